@@ -7,7 +7,18 @@ tol 1e-8, b = A*1, x0 = 0.  One step = one full solve (device-resident b, x;
 the ILU factorization and H2D copies are setup, outside the timed region).
 
 value = inner (Arnoldi) iterations of all ranks / max-over-ranks wall time.
-roofline: the single kernel with the most time over the timed region: the
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what that figure
+needs and nothing else: set-up, W warm-up steps, the N timed steps, the outputs
+of the last timed step if --dump-outputs DIR is given (DIR/<name>.npy, float64,
+at most 64 MB in all, rank 0's; the inputs are seeded, so two builds run with
+the same arguments can be compared array by array), and the result line.
+Everything below that takes runs or launches of its own -- the per-kernel
+breakdown and the rooflines (event brackets, a profiled warm-up step), the
+isolated SpMV, the exchange latencies of the sharded solve, the CPU baselines
+-- is measured under --full only; without it those fields are null / empty.
+
+roofline (--full): the single kernel with the most time over the timed region: the
 candidates (single-kernel families within 2x of the largest in a profiled
 warmup step) are each bracketed with hipEvent pairs in a rotating share of the
 timed solves, on the solver's stream (gg_profile_*), and every candidate's
@@ -83,9 +94,18 @@ def parse():
                    help="c2 only: ILU(k) factors (device numeric phase); k = 1, 2 run the skewed wavefront")
     p.add_argument("--tol", type=float, default=1e-8)
     p.add_argument("--max-iter", type=int, default=20000)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: per-kernel breakdown and "
+                        "rooflines (event brackets, a profiled warm-up step), the isolated SpMV, the "
+                        "sharded solve's exchange latencies, the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed (the solution and the "
+                        "solve's result record; c5: states and port waveforms; c3: y = A*1) as "
+                        "DIR/<name>.npy, float64, at most 64 MB in all (a seeded sample of a larger "
+                        "array); rank 0's at N > 1")
     p.add_argument("--cpu-iters", type=int, default=120,
-                   help="oracle iterations timed for cpu_baseline (0 = skip)")
-    p.add_argument("--no-profile", action="store_true", help="do not bracket kernels with events")
+                   help="--full: oracle iterations timed for cpu_baseline (0 = skip)")
+    p.add_argument("--no-profile", action="store_true", help="--full: do not bracket kernels with events")
     p.add_argument("--c3-spmvs", type=int, default=20, help="SpMV launches per c3 step")
     p.add_argument("--c4-grid", type=int, default=216, help="C4: grid points per side (216^3 = 10.1M rows)")
     p.add_argument("--dd-parts", type=int, default=8,
@@ -137,7 +157,39 @@ def parse():
     a = p.parse_args()
     if a.dd_comm == "loopback" and (a.gpus > 1 or not 0 <= a.dd_rank < a.dd_parts):
         p.error("--dd-comm loopback times one rank alone: --gpus 1 and 0 <= --dd-rank < --dd-parts")
+    if not a.full:
+        # a plain run: no event brackets, no profiled step, no CPU baseline
+        a.no_profile = True
+        a.cpu_iters = 0
     return a
+
+
+DUMP_CAP = 64 << 20            # --dump-outputs: bytes in all
+DUMP_SEED = 20261015
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: array} -> dirname/<name>.npy, float64, C order.
+    The arrays share DUMP_CAP bytes, the smallest served first; one beyond its
+    share is stored as a fixed sample of its flattened values (ascending
+    indices drawn by default_rng(DUMP_SEED) for that length and count, so the
+    same positions in every run and every build)."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_CAP
+    todo = sorted(arrays.items(), key=lambda kv: np.asarray(kv[1]).size)
+    for k, (name, arr) in enumerate(todo):
+        arr = np.ascontiguousarray(arr, np.float64)
+        share = left // (len(todo) - k) // 8
+        if arr.size > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(arr.size, size=share, replace=False))
+            arr = arr.reshape(-1)[idx]
+        left -= arr.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
+def result_record(r):
+    """a device solve's result as a caller receives it: [ret, iters, inner, restarts, relres]"""
+    return np.array([r["ret"], r["iters"], r["inner"], r["restarts"], r["relres"]], np.float64)
 
 
 # bench family -> the kernel it times (rocprofv3 kernel names in profiles/)
@@ -366,6 +418,10 @@ def bench_c3(a, torch, dist, world, rank, local):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     value = float(tot.item()) / float(t.item()) / 1e9
+    if a.dump_outputs and rank == 0:
+        # the timed launches compute y = A*1 into the solver's workspace; the
+        # same product through gg_spmv is what a caller receives
+        dump_outputs(a.dump_outputs, {"y": s.spmv(np.ones(A.shape[0]))})
     avg_us = sum(ev_ms) / len(ev_ms) * 1e3                 # events around each launch
     ach = byt / (avg_us * 1e-6) / 1e9
     rl = np.diff(A.indptr)
@@ -570,6 +626,8 @@ def bench_dd(a, torch, dist, world, rank, local):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el_max = float(t.item())
     inner = sum(r["inner"] for r in res)          # one system: every rank counts the same
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"x": dx.cpu().numpy(), "result": result_record(res[-1])})
     roof = None
     wi = d.info()["wave_interior"]
     fused_halo = (((world > 1 and comm == "ipc") or (world == 1 and comm == "loopback"))
@@ -600,7 +658,8 @@ def bench_dd(a, torch, dist, world, rank, local):
     # the exchange every sharded operator and dot pays, timed after the timed
     # region: one dot's G partials, and CGS2's (i+1) G at i = 15
     info_g = d.dot_layout(rank if world > 1 else a.dd_rank if loop else 0)[1]
-    xch = {f"{c}_doubles_us": round(d.time_exchange(c, reps=200), 2) for c in (info_g, 16 * info_g)}
+    xch = ({f"{c}_doubles_us": round(d.time_exchange(c, reps=200), 2) for c in (info_g, 16 * info_g)}
+           if a.full else None)
     out = {
         "metric": METRIC, "value": round(inner / el_max, 3), "unit": "iterations/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -801,7 +860,8 @@ def main():
             r = s.transient_batch(a.c5_steps, h5, cdiag, scen, ports, X0, restart=a.restart,
                                   max_iter=a.max_iter, tol=a.tol)
             tot = sum(r["iters_total"])
-            return dict(inner=tot, iters=tot, relres=None, ret=r["ret"])
+            return dict(inner=tot, iters=tot, relres=None, ret=r["ret"],
+                        arrays={"x": r["x"], "ports": r["ports"], "iters_total": r["iters_total"]})
         if c5:
             out = [None] * len(solvers)
 
@@ -820,7 +880,9 @@ def main():
                 for t in th:
                     t.join()
             tot = sum(r["iters_total"] for r in out)
-            return dict(inner=tot, iters=tot, relres=None, ret=max(r["ret"] for r in out))
+            return dict(inner=tot, iters=tot, relres=None, ret=max(r["ret"] for r in out),
+                        arrays={"x": np.stack([r["x"] for r in out]), "ports": np.stack([r["ports"] for r in out]),
+                                "iters_total": [r["iters_total"] for r in out]})
         dx.zero_()
         torch.cuda.synchronize()
         return s.solve_device(db.data_ptr(), dx.data_ptr(), restart=a.restart,
@@ -930,6 +992,9 @@ def main():
         dist.all_reduce(it, op=dist.ReduceOp.SUM)
     el_max, inner_all = float(t.item()), float(it.item())
     value = inner_all / el_max
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res[-1]["arrays"] if c5 else
+                     {"x": dx.cpu().numpy(), "result": result_record(res[-1])})
     if not a.no_profile and not fam:
         fam = profiled_pass()
 
@@ -1051,10 +1116,12 @@ def main():
                  for k, (r, l) in roofs.items()}
     spmv_bytes = s.bytes_spmv()
     # isolated SpMV (4 rotating copies of A, x, y: > 256 MiB, not Infinity-Cache served)
-    spmv_iso_ms = s.time_spmv(reps=100, nrot=4)
-    spmv_iso = {"avg_us": round(spmv_iso_ms * 1e3, 3),
-                "achieved_gbs": round(spmv_bytes / (spmv_iso_ms * 1e-3) / 1e9, 1),
-                "frac": round(spmv_bytes / (spmv_iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    spmv_iso = None
+    if a.full:
+        spmv_iso_ms = s.time_spmv(reps=100, nrot=4)
+        spmv_iso = {"avg_us": round(spmv_iso_ms * 1e3, 3),
+                    "achieved_gbs": round(spmv_bytes / (spmv_iso_ms * 1e-3) / 1e9, 1),
+                    "frac": round(spmv_bytes / (spmv_iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
 
     # ---- CPU baseline (rank 0, N=1): the oracle restatement -----------------------
     cpu = cpu_mt = None

@@ -66,7 +66,9 @@ def test_reference_boundary_classes_exported(ggmres_lib):
 
 
 @pytest.mark.parametrize("prog, sym", [
-    ("pg_driver", "gmresInterfacePGfloat::GMRES_dev_PG()"),
+    # (its own id: the symbol's "::" is the separator of a test id)
+    pytest.param("pg_driver", "gmresInterfacePGfloat::GMRES_dev_PG()",
+                 id="pg_driver-gmresInterfacePGfloat.GMRES_dev_PG()"),
     ("wrapper_driver", "wrapperGMRESforPG(ucr_cs_dl*, ucr_cs_dl*, ucr_cs_dl*, ucr_cs_dl*, int*, int, gpuETBR*)"),
     ("engine_driver", "GMRESilu_GPU(float*, int*, int*, int, float*, float*, int, int, int*, float*, "
                       "Preconditioner&)"),

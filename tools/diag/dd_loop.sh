@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 export PYTHONUNBUFFERED=1
 TAG=$1; O=gpurun_out/$TAG; mkdir -p $O
 for g in ${2:-c2 c4}; do for P in ${3:-2 4 8}; do for o in ${4:-cgs2 mgs}; do
-  timeout -k 10 240 python -u bench.py --workload dd --dd-comm loopback --dd-grid $g --dd-parts $P --dd-orth $o \
+  timeout -k 10 240 python -u bench.py --full --workload dd --dd-comm loopback --dd-grid $g --dd-parts $P --dd-orth $o \
       --steps 2 --warmup 1 --cpu-iters 0 > $O/loop_${g}_${P}_$o.json 2> $O/loop_${g}_${P}_$o.err
   python3 -c "
 import json; d=json.loads(open('$O/loop_${g}_${P}_$o.json').read().strip().splitlines()[-1])

@@ -14,9 +14,9 @@ for v in "$@"; do
   timeout -k 10 200 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_border.py -x -q --timeout 120 \
       --timeout-method thread -m gpu -k "split or flow or pg or border or iluk" > $OUT/tests_$v.log 2>&1
   tail -1 $OUT/tests_$v.log
-  timeout -k 10 200 python -u bench.py --workload pg --pg-perm random --steps 3 --warmup 1 --cpu-iters 0 \
+  timeout -k 10 200 python -u bench.py --full --workload pg --pg-perm random --steps 3 --warmup 1 --cpu-iters 0 \
       > $OUT/pgr_$v.json 2> $OUT/pgr_$v.err
-  timeout -k 10 300 python -u bench.py --workload c3s --ilu-level 1 --steps 1 --warmup 1 --cpu-iters 0 --max-iter 600 \
+  timeout -k 10 300 python -u bench.py --full --workload c3s --ilu-level 1 --steps 1 --warmup 1 --cpu-iters 0 --max-iter 600 \
       > $OUT/c3s1_$v.json 2> $OUT/c3s1_$v.err
   timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch_$v -o run -f csv -- \
       python3 -u bench.py --workload pg --pg-perm random --steps 1 --warmup 0 --cpu-iters 0 --no-profile \

@@ -10,7 +10,7 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_fastdiv.py tests/test_gpu_p
 tail -1 $O/tests.log
 for k in 1 2; do
   for v in 1 0; do
-    GG_FMA_SKEW=$v timeout -k 10 300 python -u bench.py --ilu-level $k --steps 2 --warmup 1 --cpu-iters 0 \
+    GG_FMA_SKEW=$v timeout -k 10 300 python -u bench.py --full --ilu-level $k --steps 2 --warmup 1 --cpu-iters 0 \
         > $O/c2_ilu${k}_s$v.json 2> $O/c2_ilu${k}_s$v.err
     python3 -c "
 import json; d=json.loads(open('$O/c2_ilu${k}_s$v.json').read().strip().splitlines()[-1]); k=d['kernels']

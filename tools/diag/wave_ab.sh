@@ -15,7 +15,7 @@ done
 for rep in 1 2; do
   for v in base "$@"; do
     if [ "$v" = base ]; then lib=""; else lib="$PWD/abvar/libggmres_$v.so"; fi
-    GGMRES_LIB=$lib timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --cpu-iters 0 \
+    GGMRES_LIB=$lib timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --cpu-iters 0 \
         > $O/c2_${v}_$rep.json 2> $O/c2_${v}_$rep.err
     python3 -c "
 import json; d=json.loads(open('$O/c2_${v}_$rep.json').read().strip().splitlines()[-1])

@@ -16,9 +16,9 @@ ARGS=""
 [ "$WL" = c3s_ilu1 ] && ARGS="--workload c3s --ilu-level 1"     # C3's own preconditioner on the stand-in
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 python -u bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/bench.json 2> $OUT/bench.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run -f csv -- \
-    python3 -u bench.py $ARGS --steps 1 --warmup 1 --cpu-iters 0 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+    python3 -u bench.py --full $ARGS --steps 1 --warmup 1 --cpu-iters 0 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o run -f csv -- \
     python3 -u bench.py $ARGS --steps 1 --warmup 0 --cpu-iters 0 --max-iter 600 --no-profile > /dev/null 2> $OUT/fetch.err
 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/write -o run -f csv -- \
