@@ -90,6 +90,17 @@ void iluk_emit(const std::vector<std::vector<int>> &Lja, const std::vector<std::
                const std::vector<std::vector<double>> &Lma, const std::vector<std::vector<double>> &Uma,
                const std::vector<double> &Draw, Csr &L, Csr &U);
 
+// AINV (host/ainv.cpp): cusp's nonsym_bridson_ainv as MyAINV::Initilize calls it
+// (src/preconditioner.cu:166), fp64, drop tolerance tol, no bound on a row's
+// entries.  M = Wt diag(dinv) Z ~ A^-1, Z unit lower and Wt unit upper
+// triangular, ascending columns.  GG_OK, GG_EZEROPIVOT (a pivot 0 or not
+// finite) or GG_EINVAL (tol negative or NaN)
+int ainv_bridson(const Csr &A, double tol, Csr &Z, Csr &Wt, std::vector<double> &dinv);
+// MyDIAG::Initilize (src/preconditioner.cu:506-540): inv[i] = 1 / the entry of
+// row i whose column is nearest the diagonal (the first of equally near ones);
+// GG_EZEROPIVOT for an empty row or a zero value
+int diag_nearest(const Csr &A, std::vector<double> &inv);
+
 // canonical forms (host/analysis.cpp)
 CanonTri canon_lower_unit(const Csr &L);        // LUSolve_ignoreZero forward (diag never applied)
 CanonTri canon_upper_ignorezero(const Csr &U);  // LUSolve_ignoreZero backward

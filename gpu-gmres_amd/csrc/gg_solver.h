@@ -63,6 +63,12 @@ struct gg_solver {
     // y_out[r] = lay(prow^-1[r])
     DBuf<long long> sb_map, sx_map, sx_out, sy_out;
     DevCsr dUfull;        // the split U factor (diagonal first) in layout space (apply_start)
+    // AINV / DIAG (gg_set_precond_ainv / _diag; natural order): M = Wt diag(dinv) Z
+    // applied as two products; DIAG keeps its reciprocals in ainv_d
+    DevCsr aZ, aWt;
+    DBuf<double> ainv_d;
+    double ainv_bytes = 0;              // algorithmic bytes per application
+    long long ainv_nnz[2] = {0, 0};     // nnz(Z), nnz(Wt)
     // caller-supplied preconditioner (gg_set_precond_user): fp32 staging of its
     // device arrays, natural order
     gg_precond_fn ufn = nullptr;

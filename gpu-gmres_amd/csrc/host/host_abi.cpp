@@ -68,6 +68,50 @@ int gg_host_iluk(int level, int n, const int *rp, const int *ci, const double *v
     }
 }
 
+// row_ptr monotone from 0, arrays present, columns in [0, n)
+static bool csr_ok(int n, const int *rp, const int *ci, const double *v)
+{
+    if (n < 0 || !rp || rp[0] != 0) return false;
+    for (int r = 0; r < n; r++)
+        if (rp[r + 1] < rp[r]) return false;
+    if (n > 0 && rp[n] > 0 && (!ci || !v)) return false;
+    for (int k = 0; k < (n > 0 ? rp[n] : 0); k++)
+        if (ci[k] < 0 || ci[k] >= n) return false;
+    return true;
+}
+
+int gg_host_ainv(int n, const int *rp, const int *ci, const double *v, double drop_tol, int *z_rp, int **z_ci,
+                 double **z_v, int *wt_rp, int **wt_ci, double **wt_v, double *dinv)
+{
+    if (!z_rp || !wt_rp || !z_ci || !z_v || !wt_ci || !wt_v || !dinv || !csr_ok(n, rp, ci, v)) return GG_EINVAL;
+    try {
+        Csr Z, Wt;
+        std::vector<double> d;
+        const int rc = ainv_bridson(wrap(n, rp, ci, v), drop_tol, Z, Wt, d);
+        if (rc) return rc;
+        emit(Z, z_rp, z_ci, z_v);
+        emit(Wt, wt_rp, wt_ci, wt_v);
+        std::copy(d.begin(), d.end(), dinv);
+        return GG_OK;
+    } catch (...) {
+        return GG_EINVAL;
+    }
+}
+
+int gg_host_diag(int n, const int *rp, const int *ci, const double *v, double *inv)
+{
+    if (!inv || !csr_ok(n, rp, ci, v)) return GG_EINVAL;
+    try {
+        std::vector<double> d;
+        const int rc = diag_nearest(wrap(n, rp, ci, v), d);
+        if (rc) return rc;
+        std::copy(d.begin(), d.end(), inv);
+        return GG_OK;
+    } catch (...) {
+        return GG_EINVAL;
+    }
+}
+
 int gg_host_iluk_pattern(int level, int n, const int *rp, const int *ci, int threads, int *prow, int **pcol)
 {
     if (n < 0 || level < 0 || !rp || !prow || !pcol) return GG_EINVAL;

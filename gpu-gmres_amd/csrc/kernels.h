@@ -230,8 +230,9 @@ void launch_div(Gate g, const double *in, const double *s, double *out, int n, h
 // ---- SpMV ------------------------------------------------------------------
 // y = A x  (resid=false)  or  y = b - A x  (resid=true)
 // y = A x (resid: y = b - A x); ydiv: y[r] /= ydiv[r] (the split engine's folded row scaling)
+// ymul (alone): y[r] = (A x)[r] * ymul[r] (AINV's diagonal folded into its first product)
 void launch_spmv(Gate g, const DevCsr &A, const double *x, const double *b, double *y, bool resid,
-                 hipStream_t st, const double *ydiv = nullptr);
+                 hipStream_t st, const double *ydiv = nullptr, const double *ymul = nullptr);
 // y[r] = (sum_k a_k RN(x[c_k] / xdiv[c_k])) / ydiv[r] on the sliced copy (false, nothing
 // launched, when A has none): the split engine's D_r^-1 in the SpMV's gathers
 bool launch_spmv_xdiv(Gate g, const DevCsr &A, const double *x, const double *xdiv, double *y, hipStream_t st,

@@ -485,10 +485,12 @@ __device__ __forceinline__ double ld_x(const double *p)
     if constexpr (XA) return __longlong_as_double((long long)ld_agent(reinterpret_cast<const unsigned long long *>(p)));
     else return *p;
 }
-template <bool RESID, bool YDIV, bool XA = false>
+// YMUL: y[r] = (the row's result) * ymul[r] -- AINV's diagonal folded into its
+// first product (MyAINV::HostPrecond's temp[i] = o_data[i] * diag_val[i])
+template <bool RESID, bool YDIV, bool XA = false, bool YMUL = false>
 __device__ __forceinline__ void spmv_stream_block(int bid, const int *blk, const int *rp, const int *ci,
                                                   const double *v, const double *x, const double *b, double *y,
-                                                  const double *ydiv)
+                                                  const double *ydiv, const double *ymul = nullptr)
 {
     constexpr int U = kSpmvCap / kBlock;        // products per thread
     __shared__ double prod[kSpmvCap];
@@ -508,7 +510,7 @@ __device__ __forceinline__ void spmv_stream_block(int bid, const int *blk, const
         acc = block_sum(acc);
         if (tid == 0) {
             const double o = RESID ? (-1.0 * acc + 1.0 * b[r0]) : acc;
-            y[r0] = YDIV ? o / ydiv[r0] : o;
+            y[r0] = YDIV ? o / ydiv[r0] : YMUL ? o * ymul[r0] : o;
         }
         return;
     }
@@ -562,7 +564,7 @@ __device__ __forceinline__ void spmv_stream_block(int bid, const int *blk, const
         for (; e < z; e++) acc += prod[e];
         const int r = r0 + tid;
         const double o = RESID ? (-1.0 * acc + 1.0 * b[r]) : acc;
-        y[r] = YDIV ? o / ydiv[r] : o;
+        y[r] = YDIV ? o / ydiv[r] : YMUL ? o * ymul[r] : o;
     }
 }
 template <bool RESID, bool YDIV = false>
@@ -573,6 +575,14 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream(Gate g, const int *blk, 
 {
     if (gated(g)) return;
     spmv_stream_block<RESID, YDIV>(blockIdx.x, blk, rp, ci, v, x, b, y, ydiv);
+}
+// y = (A x) o ymul
+__global__ __launch_bounds__(kBlock) void k_spmv_stream_mul(Gate g, const int *blk, const int *rp, const int *ci,
+                                                            const double *v, const double *x, double *y,
+                                                            const double *ymul)
+{
+    if (gated(g)) return;
+    spmv_stream_block<false, false, false, true>(blockIdx.x, blk, rp, ci, v, x, nullptr, y, nullptr, ymul);
 }
 
 // Sliced ELL: one wave per 64-row slice, lane = row; the slice's entries are
@@ -596,11 +606,13 @@ __device__ __forceinline__ int xcd_block()
 
 // XDIV: x[c] = RN(x[c] / xdiv[c]) formed per gathered term -- the split
 // engine's D_r^-1 pass (k_div) folded into the gathers, the same division
-template <bool RESID, bool YDIV, bool XDIV, bool XA = false>
+// YMUL: y[r] = (the row's result) * ymul[r] (AINV's diagonal)
+template <bool RESID, bool YDIV, bool XDIV, bool XA = false, bool YMUL = false>
 __device__ __forceinline__ void spmv_sell_slice(int s, int n, const int *sptr, const int *__restrict__ ci,
                                                 const double *__restrict__ v, const double *x,
                                                 const double *__restrict__ b, double *__restrict__ y,
-                                                const double *__restrict__ ydiv, const double *__restrict__ xdiv)
+                                                const double *__restrict__ ydiv, const double *__restrict__ xdiv,
+                                                const double *__restrict__ ymul = nullptr)
 {
     const int lane = threadIdx.x & 63;
     const int off = sptr[s], w = (sptr[s + 1] - off) >> 6;
@@ -635,7 +647,7 @@ __device__ __forceinline__ void spmv_sell_slice(int s, int n, const int *sptr, c
     const int r = s * 64 + lane;
     if (r < n) {
         const double o = RESID ? (-1.0 * acc + 1.0 * b[r]) : acc;
-        y[r] = YDIV ? o / ydiv[r] : o;
+        y[r] = YDIV ? o / ydiv[r] : YMUL ? o * ymul[r] : o;
     }
 }
 template <bool RESID, bool YDIV = false, bool XDIV = false>
@@ -659,6 +671,17 @@ __global__ __launch_bounds__(kBlock) void k_spmv_sell(Gate g, int n, int nslice,
         if (fill && r < nfill) fill[r] = kSentinel;
     }
     spmv_sell_slice<RESID, YDIV, XDIV>(s, n, sptr, ci, v, x, b, y, ydiv, xdiv);
+}
+// y = (A x) o ymul
+__global__ __launch_bounds__(kBlock) void k_spmv_sell_mul(Gate g, int n, int nslice, const int *sptr,
+                                                          const int *__restrict__ ci, const double *__restrict__ v,
+                                                          const double *__restrict__ x, double *__restrict__ y,
+                                                          const double *__restrict__ ymul)
+{
+    if (gated(g)) return;
+    const int s = xcd_block() * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (s >= nslice) return;
+    spmv_sell_slice<false, false, false, false, true>(s, n, sptr, ci, v, x, nullptr, y, nullptr, nullptr, ymul);
 }
 
 // Column-panel SpMV, one launch per panel p (DevCsr::panel): a block owns a
@@ -5352,9 +5375,18 @@ void launch_div(Gate g, const double *in, const double *s, double *out, int n, h
 }
 
 void launch_spmv(Gate g, const DevCsr &A, const double *x, const double *b, double *y, bool resid,
-                 hipStream_t st, const double *ydiv)
+                 hipStream_t st, const double *ydiv, const double *ymul)
 {
     if (A.nblk == 0) return;
+    if (ymul) {
+        // y = (A x) o ymul (AINV's first product): the sliced or the CSR-stream kernel
+        if (A.sell)
+            k_spmv_sell_mul<<<(A.nslice + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, st>>>(
+                g, A.n, A.nslice, A.sptr.p, A.sci.p, A.sv.p, x, y, ymul);
+        else
+            k_spmv_stream_mul<<<A.nblk, kBlock, 0, st>>>(g, A.blk.p, A.rp.p, A.ci.p, A.v.p, x, y, ymul);
+        return;
+    }
     if (A.panel && A.rtile && !resid && !ydiv && x != y) {
         // row tiles: one launch, each block its rows' segments panel by panel
         k_spmv_rtile<<<A.rtile, kBlock, 0, st>>>(g, A.rt_sub.p, A.pblk.p, A.seg_row.p, A.seg_ptr.p, A.pci.p, A.pv.p, x,

@@ -862,6 +862,18 @@ void apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i = -1)
         launch_copy(in, out, s->Ppad, s->st);   // copy is not gated: harmless
         return;
     }
+    if (s->pkind == GG_PRECOND_DIAG) {
+        launch_mul(g, in, s->ainv_d.p, out, s->A.n, s->st);      // MyDIAG::HostPrecond
+        return;
+    }
+    if (s->pkind == GG_PRECOND_AINV) {
+        // out = Wt (dinv o (Z in)) (MyAINV::HostPrecond): two products, the
+        // diagonal in the first one's store (a one-launch form measured slower
+        // and was not kept: DESIGN.md "AINV / DIAG")
+        launch_spmv(g, s->aZ, in, nullptr, s->t1.p, false, s->st, nullptr, s->ainv_d.p);
+        launch_spmv(g, s->aWt, s->t1.p, nullptr, out, false, s->st);
+        return;
+    }
     trsv(s, g, s->L, GG_PROF_TRSV_L, i, in, s->t1.p);
     trsv(s, g, s->U, GG_PROF_TRSV_U, i, s->t1.p, out);
 }
@@ -1348,11 +1360,13 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
     s->shared = (opt->flags & GG_SOLVE_SHARED_DEVICE) != 0;
     if (s->shared) {
         // only kernels whose workgroups wait on earlier-dispatched ones
-        bool ok = s->pkind == GG_PRECOND_NONE;
-        if (s->pkind != GG_PRECOND_SPLIT && s->pkind != GG_PRECOND_NONE)
+        // (AINV / DIAG: SpMV and elementwise launches, nothing waits)
+        const bool nowait = s->pkind == GG_PRECOND_NONE || s->pkind == GG_PRECOND_AINV || s->pkind == GG_PRECOND_DIAG;
+        bool ok = nowait;
+        if (s->pkind != GG_PRECOND_SPLIT && !nowait)
             ok = s->L.kind == DevTri::WAVE2D && s->U.kind == DevTri::WAVE2D && s->L.wl.nz == 1;
         GG_REQUIRE(ok, GG_EINVAL, "gg_solve: GG_SOLVE_SHARED_DEVICE needs the 2D wavefront path "
-                                  "(or no preconditioner)");
+                                  "(or AINV, DIAG or no preconditioner)");
     }
     const int n = s->A.n;
     set_device(s);
@@ -1733,6 +1747,77 @@ int gg_set_precond_none(gg_solver *s)
     GG_HIP(hipStreamSynchronize(s->st));
     return GG_OK;
     GG_API_END
+}
+
+// gg_bytes_spmv's CSR formulation for one factor
+static double csr_spmv_bytes(const Csr &M) { return 12.0 * M.nnz() + 4.0 * (M.n + 1.0) + 16.0 * M.n; }
+
+// AINV (MyAINV, src/preconditioner.h:87-116): the factors on the host
+// (host/ainv.cpp), uploaded as SpMV operands in the natural-order space
+// (sliced or CSR-stream, DevCsr::upload's choice for each factor)
+int gg_set_precond_ainv(gg_solver *s, double drop_tol)
+{
+    GG_API_BEGIN
+    GG_REQUIRE(s && s->have_A, GG_ESTATE, "set_precond before set_matrix");
+    GG_REQUIRE(drop_tol >= 0.0, GG_EINVAL, "gg_set_precond_ainv: drop_tol must be >= 0");
+    set_device(s);
+    Csr Z, Wt;
+    std::vector<double> dinv;
+    const int rc = ainv_bridson(s->A, drop_tol, Z, Wt, dinv);
+    GG_REQUIRE(rc == GG_OK, rc, rc == GG_EZEROPIVOT ? "AINV: zero or non-finite pivot" : "AINV: construction failed");
+    setup_space(s, nullptr);
+    s->L.kind = s->U.kind = DevTri::NONE;
+    s->aZ.upload(Z, s->st);
+    s->aWt.upload(Wt, s->st);
+    s->ainv_d.upload(dinv, s->st);
+    s->ainv_bytes = csr_spmv_bytes(Z) + csr_spmv_bytes(Wt) + 8.0 * s->A.n;
+    s->ainv_nnz[0] = Z.nnz();
+    s->ainv_nnz[1] = Wt.nnz();
+    s->pkind = GG_PRECOND_AINV;
+    GG_HIP(hipStreamSynchronize(s->st));
+    return GG_OK;
+    GG_API_END
+}
+
+// DIAG (MyDIAG, src/preconditioner.h:321-339): out = in * inv, natural order
+int gg_set_precond_diag(gg_solver *s)
+{
+    GG_API_BEGIN
+    GG_REQUIRE(s && s->have_A, GG_ESTATE, "set_precond before set_matrix");
+    set_device(s);
+    std::vector<double> inv;
+    const int rc = diag_nearest(s->A, inv);
+    GG_REQUIRE(rc == GG_OK, rc, "DIAG: a row is empty or its entry nearest the diagonal is zero");
+    setup_space(s, nullptr);
+    s->L.kind = s->U.kind = DevTri::NONE;
+    s->ainv_d.upload(inv, s->st);
+    s->ainv_bytes = 24.0 * s->A.n;      // in, inv, out
+    s->pkind = GG_PRECOND_DIAG;
+    GG_HIP(hipStreamSynchronize(s->st));
+    return GG_OK;
+    GG_API_END
+}
+
+// no one-launch apply in this build (it measured slower than the two launches
+// and was deleted: DESIGN.md "AINV / DIAG")
+int gg_ainv_fused(gg_solver *) { return 0; }
+
+long long gg_ainv_nnz(gg_solver *s, int which)
+{
+    if (!s || s->pkind != GG_PRECOND_AINV || (which != 0 && which != 1)) {
+        set_error("gg_ainv_nnz: the preconditioner is not AINV, or which is not 0 / 1");
+        return GG_EINVAL;
+    }
+    return s->ainv_nnz[which];
+}
+
+int gg_ainv_sliced(gg_solver *s, int which)
+{
+    if (!s || s->pkind != GG_PRECOND_AINV || (which != 0 && which != 1)) {
+        set_error("gg_ainv_sliced: the preconditioner is not AINV, or which is not 0 / 1");
+        return GG_EINVAL;
+    }
+    return (which == 0 ? s->aZ.sell : s->aWt.sell) ? 1 : 0;
 }
 
 static void setup_left(gg_solver *s, const Csr &Lf, const Csr &Uf, int kind)
@@ -2725,6 +2810,7 @@ double gg_bytes_spmv(gg_solver *s)
 double gg_bytes_precond(gg_solver *s)
 {
     if (!s || s->pkind < 0) return 0.0;
+    if (s->pkind == GG_PRECOND_AINV || s->pkind == GG_PRECOND_DIAG) return s->ainv_bytes;
     s->L.fast = s->U.fast = s->div_mode;
     return s->L.alg_bytes() + s->U.alg_bytes();
 }
@@ -2732,6 +2818,7 @@ double gg_bytes_precond(gg_solver *s)
 double gg_bytes_trsv(gg_solver *s, int which)
 {
     if (!s || s->pkind < 0 || (which != 0 && which != 1)) return 0.0;
+    if (s->pkind == GG_PRECOND_AINV || s->pkind == GG_PRECOND_DIAG) return 0.0;   // no triangles
     s->L.fast = s->U.fast = s->div_mode;
     return which == 0 ? s->L.alg_bytes() : s->U.alg_bytes();
 }
@@ -2739,6 +2826,7 @@ double gg_bytes_trsv(gg_solver *s, int which)
 double gg_bytes_trsv_stream(gg_solver *s, int which)
 {
     if (!s || s->pkind < 0 || (which != 0 && which != 1)) return 0.0;
+    if (s->pkind == GG_PRECOND_AINV || s->pkind == GG_PRECOND_DIAG) return 0.0;
     s->L.fast = s->U.fast = s->div_mode;
     return which == 0 ? s->L.stream_alg_bytes() : s->U.stream_alg_bytes();
 }

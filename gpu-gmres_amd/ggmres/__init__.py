@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("GGMRES_LIB") or os.path.join(PKG_ROOT, "lib", "libggm
 
 GG_OK, GG_NOT_CONVERGED = 0, 1
 PRECOND_NONE, PRECOND_ILU0, PRECOND_ILUK, PRECOND_LU, PRECOND_SPLIT, PRECOND_USER, PRECOND_USER_SPLIT = range(7)
+PRECOND_AINV, PRECOND_DIAG = 7, 8
 APPLY_MINV, APPLY_LEFT, APPLY_RIGHT, APPLY_START, APPLY_RHS = range(5)
 SOLVE_SHARED_DEVICE = 0x1     # gg_options.flags: other solvers share the device (ggmres.h)
 SOLVE_CGS2 = 0x2              # gg_options.flags: CGS2 orthogonalization (sharded solve only)
@@ -35,6 +36,7 @@ EXPORTS = [
     "gg_trsv_kernel", "gg_mgs_kernel", "gg_set_precond_user", "gg_solve_device_f32",
     "gg_device_fingerprint", "gg_set_matrix_count", "gg_trsv_levels", "gg_layout", "gg_reduce_blocks",
     "gg_solve_batch_device", "gg_solve_batch", "gg_batch_engine", "gg_batch_history", "gg_transient_batch",
+    "gg_set_precond_ainv", "gg_set_precond_diag", "gg_ainv_fused", "gg_ainv_nnz", "gg_ainv_sliced",
 ]
 # gg_precond_fn: int (*)(void *ctx, int op, const float *in, float *out, int n), device arrays
 PRECOND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -85,6 +87,12 @@ def lib():
                   "gg_uses_wavefront", "gg_spmv_sliced", "gg_set_precond_ilu0_device", "gg_spmv_panels",
                   "gg_spmv_rtile"):
             getattr(L, f).argtypes = [_VP]
+        for f in ("gg_set_precond_diag", "gg_ainv_fused"):
+            getattr(L, f).argtypes = [_VP]
+        L.gg_set_precond_ainv.argtypes = [_VP, ctypes.c_double]
+        L.gg_ainv_nnz.argtypes = [_VP, ctypes.c_int]
+        L.gg_ainv_nnz.restype = ctypes.c_longlong
+        L.gg_ainv_sliced.argtypes = [_VP, ctypes.c_int]
         L.gg_set_precond_iluk.argtypes = [_VP, ctypes.c_int]
         L.gg_set_division.argtypes = [_VP, ctypes.c_int]
         L.gg_division_active.argtypes = [_VP, ctypes.c_int]
@@ -214,6 +222,29 @@ class Solver:
         ms = ctypes.c_double()
         _check(lib().gg_ilu0_device_values(self.h, out, ctypes.byref(ms)))
         return out, ms.value
+
+    def set_precond_ainv(self, drop_tol=0.1):
+        """AINV (MyAINV: cusp's nonsym_bridson_ainv at the reference's drop
+        tolerance .1), applied as two SpMV launches"""
+        _check(lib().gg_set_precond_ainv(self.h, float(drop_tol)))
+
+    def set_precond_diag(self):
+        """DIAG (MyDIAG): out = in / (the entry of each row nearest the diagonal)"""
+        _check(lib().gg_set_precond_diag(self.h))
+
+    @property
+    def ainv_fused(self):
+        """1 when a one-launch kernel serves the AINV apply (gg_ainv_fused; 0 in
+        this build: the two launches measured faster)"""
+        return int(lib().gg_ainv_fused(self.h))
+
+    def ainv_nnz(self):
+        """(nnz(Z), nnz(Wt)) of the AINV factors"""
+        return tuple(int(_check(lib().gg_ainv_nnz(self.h, w), allow_nc=True)) for w in (0, 1))
+
+    def ainv_sliced(self):
+        """(Z, Wt): 1 where the AINV factor runs on the sliced-ELL SpMV kernel, 0 on CSR-stream"""
+        return tuple(int(_check(lib().gg_ainv_sliced(self.h, w), allow_nc=True)) for w in (0, 1))
 
     def set_precond_iluk(self, level):
         _check(lib().gg_set_precond_iluk(self.h, int(level)))

@@ -5,7 +5,7 @@ import ctypes
 import numpy as np
 import scipy.sparse as sp
 
-from . import _check, _csr_arrays, lib
+from . import GGError, _check, _csr_arrays, lib
 
 PART_BISECT, PART_BLOCKS, PART_GRID, PART_COLOR_SEP = 0, 1, 2, 4
 _PI = ctypes.POINTER(ctypes.c_int)
@@ -73,6 +73,38 @@ def dd_form(B, begin, nparts):
     E = [block(B, int(begin[k]), int(begin[k + 1]), s0, s1) for k in range(nparts)]
     F = [block(B, s0, s1, int(begin[k]), int(begin[k + 1])) for k in range(nparts)]
     return As, E, F, block(B, s0, s1, s0, s1)
+
+
+def ainv(A, drop_tol=0.1):
+    """The AINV factors of A (gg_host_ainv: cusp's nonsym_bridson_ainv in fp64,
+    MyAINV::Initilize, src/preconditioner.cu:166) -> (Z, Wt, dinv): scipy CSR Z
+    (unit lower) and Wt (unit upper), M = Wt diag(dinv) Z ~ A^-1.  No device."""
+    n, rp, ci, v = _csr_arrays(A)
+    zrp = np.zeros(n + 1, np.int32)
+    wrp = np.zeros(n + 1, np.int32)
+    dinv = np.zeros(max(n, 1))
+    zci, zv, wci, wv = _PI(), _PD(), _PI(), _PD()
+    f = lib().gg_host_ainv
+    f.argtypes = [ctypes.c_int, _PI, _PI, _PD, ctypes.c_double, _PI, ctypes.POINTER(_PI), ctypes.POINTER(_PD),
+                  _PI, ctypes.POINTER(_PI), ctypes.POINTER(_PD), _PD]
+    rc = f(n, _ptr(rp, _PI), _ptr(ci, _PI), _ptr(v, _PD), float(drop_tol), _ptr(zrp, _PI), ctypes.byref(zci),
+           ctypes.byref(zv), _ptr(wrp, _PI), ctypes.byref(wci), ctypes.byref(wv), _ptr(dinv, _PD))
+    if rc != 0:
+        raise GGError(rc, "gg_host_ainv: " + lib().gg_strerror(rc).decode())
+    return _take_csr(n, n, zrp, zci, zv), _take_csr(n, n, wrp, wci, wv), dinv[:n]
+
+
+def diag(A):
+    """MyDIAG::Initilize's reciprocals (gg_host_diag): 1 / the entry of each
+    row nearest the diagonal, the first of two equally near.  No device."""
+    n, rp, ci, v = _csr_arrays(A)
+    inv = np.zeros(max(n, 1))
+    f = lib().gg_host_diag
+    f.argtypes = [ctypes.c_int, _PI, _PI, _PD, _PD]
+    rc = f(n, _ptr(rp, _PI), _ptr(ci, _PI), _ptr(v, _PD), _ptr(inv, _PD))
+    if rc != 0:
+        raise GGError(rc, "gg_host_diag: " + lib().gg_strerror(rc).decode())
+    return inv[:n]
 
 
 def read_mtx(path, expand_symmetric=False):

@@ -63,7 +63,9 @@ enum gg_precond_kind {
     GG_PRECOND_LU = 3,     /* left, caller-supplied L,U                    */
     GG_PRECOND_SPLIT = 4,  /* ILU++/PG split: Ml = L^-1 P_r D_l^-1, Mr = D_r^-1 P_c U^-1 M */
     GG_PRECOND_USER = 5,   /* caller-supplied left operator (gg_set_precond_user)          */
-    GG_PRECOND_USER_SPLIT = 6  /* caller-supplied split operators (gg_set_precond_user)     */
+    GG_PRECOND_USER_SPLIT = 6, /* caller-supplied split operators (gg_set_precond_user)     */
+    GG_PRECOND_AINV = 7,   /* left, M = Wt diag(dinv) Z built from A (gg_set_precond_ainv) */
+    GG_PRECOND_DIAG = 8    /* left, M = diag(inv) built from A (gg_set_precond_diag)       */
 };
 
 /* which operator gg_precond_apply applies */
@@ -90,7 +92,8 @@ typedef struct gg_options {
  * scenarios of a transient study).  The solve then launches no kernel that
  * needs the whole device co-resident (the orthogonalization takes the
  * per-step kernels instead of the persistent launch); it requires the 2D
- * wavefront triangular solve or no preconditioner (else GG_EINVAL), whose
+ * wavefront triangular solve, AINV / DIAG (applied by launches that wait on
+ * nothing) or no preconditioner (else GG_EINVAL); the wavefront's
  * workgroups only wait on workgroups dispatched before them; for the same
  * reason the inner iteration's SpMV stays a launch of its own (without the
  * flag it runs inside the forward solve's launch on the GG_DIV_FMA 2D path;
@@ -174,6 +177,35 @@ int gg_set_precond_split(gg_solver *s,
  * own: the engine pays a host round trip per application. */
 typedef int (*gg_precond_fn)(void *ctx, int op, const float *in, float *out, int n);
 int gg_set_precond_user(gg_solver *s, int split, gg_precond_fn fn, void *ctx);
+/* The reference's other two built-in preconditioners (its thermal drivers offer
+ * NONE / DIAG / ILU0 / AINV, src_thermal/main1.cu:338-347), both left, both in
+ * the natural-order vector space, no triangular solve: gg_trsv_kernel gives "",
+ * gg_trsv_levels 0, gg_batch_engine 0 (gg_solve_batch* runs scenario by
+ * scenario), GG_SOLVE_SHARED_DEVICE accepted.
+ *   gg_set_precond_ainv   MyAINV (src/preconditioner.h:87-116, src/preconditioner.cu:
+ *       110-201): cusp's nonsym_bridson_ainv(A, drop_tol) on the host in fp64
+ *       (gg_host_ainv; the reference passes .1), applied as MyAINV::HostPrecond,
+ *       out = Wt (dinv o (Z in)): two SpMV launches, dinv folded into the first
+ *       one's store.  As in gg_spmv, a row of a factor with at most 2048
+ *       entries is a serial sum in column order (the reference's bits); a
+ *       longer row is summed by a strided block reduction, within 1e-13 of the
+ *       serial sum on the scale |row| . |x|.  GG_EZEROPIVOT: a pivot is 0 or
+ *       not finite; GG_EINVAL: drop_tol negative or NaN.
+ *   gg_set_precond_diag   MyDIAG (src/preconditioner.h:321-339, src/preconditioner.cu:
+ *       480-540): out = in * inv, inv[i] = 1 / the entry of row i nearest the
+ *       diagonal (MyDIAG::HostPrecond).  GG_EZEROPIVOT: empty row or zero entry. */
+int gg_set_precond_ainv(gg_solver *s, double drop_tol);
+int gg_set_precond_diag(gg_solver *s);
+/* 1 when a one-launch kernel serves the AINV apply, 0 when the two SpMV
+ * launches do.  Always 0 in this build: the one-launch form (both products in
+ * a resident grid, slice flags between them) measured 26.6 us against 21.6 us
+ * for the two launches on the 1M-row grid and was not kept. */
+int gg_ainv_fused(gg_solver *s);
+/* entries of the AINV factors: which = 0 Z, 1 Wt (negative: not AINV) */
+long long gg_ainv_nnz(gg_solver *s, int which);
+/* the SpMV kernel AINV factor `which` (0 Z, 1 Wt) takes: 1 sliced ELL, 0
+ * CSR-stream (as gg_spmv_sliced says for A); negative: not AINV */
+int gg_ainv_sliced(gg_solver *s, int which);
 int gg_precond_kind(gg_solver *s);
 /* Division in the non-unit triangular solves (the reference divides,
  * LUSolve_ignoreZero src/SpMV_compute.cpp:118-133, HostPrecond_left/right

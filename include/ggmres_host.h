@@ -6,6 +6,8 @@
  * without a device:
  *   gg_host_ilu0   leftILU            src/leftILU.cu:27-336
  *   gg_host_iluk   ilukC + lofC       src/iluk.cpp:56-334
+ *   gg_host_ainv   MyAINV::Initilize (cusp nonsym_bridson_ainv)  src/preconditioner.cu:140-201
+ *   gg_host_diag   MyDIAG::Initilize  src/preconditioner.cu:506-540
  *   gg_host_wave2d / gg_host_wave3d
  *                  structured-grid detection for the wavefront SpTRSV
  *                  (replaces cusparseScsrsv_analysis, src/gmres.cu:1516-1517)
@@ -32,6 +34,23 @@ int gg_host_ilu0(int n, const int *row_ptr, const int *col_idx, const double *va
 int gg_host_iluk(int level, int n, const int *row_ptr, const int *col_idx, const double *val,
                  int *l_row_ptr, int **l_col_idx, double **l_val,
                  int *u_row_ptr, int **u_col_idx, double **u_val);
+/* The AINV preconditioner of MyAINV (src/preconditioner.h:87-116, src/preconditioner.cu:
+ * 110-201): cusp's nonsym_bridson_ainv(A, drop_tol) in fp64, no bound on the
+ * entries per row.  M = Wt diag(dinv) Z ~ A^-1 with Z unit lower and Wt unit
+ * upper triangular (ascending columns); the apply is out = Wt (dinv o (Z in))
+ * (MyAINV::HostPrecond: each row a serial sum in column order; on the device
+ * that holds for rows of at most 2048 entries, see gg_set_precond_ainv).  z_row_ptr,
+ * wt_row_ptr (n + 1) and dinv (n) caller-allocated, the col / val arrays
+ * malloc'd (gg_host_free).  GG_EZEROPIVOT: a pivot is 0 or not finite;
+ * GG_EINVAL: drop_tol negative or NaN. */
+int gg_host_ainv(int n, const int *row_ptr, const int *col_idx, const double *val, double drop_tol,
+                 int *z_row_ptr, int **z_col_idx, double **z_val,
+                 int *wt_row_ptr, int **wt_col_idx, double **wt_val, double *dinv);
+/* MyDIAG::Initilize (src/preconditioner.cu:506-540): inv[i] = 1 / the entry of
+ * row i whose column is nearest the diagonal (the first of two equally near);
+ * the apply is out = in * inv (MyDIAG::HostPrecond).  GG_EZEROPIVOT: an empty
+ * row or a zero value. */
+int gg_host_diag(int n, const int *row_ptr, const int *col_idx, const double *val, double *inv);
 /* The ILU(level) pattern as flat rows (each row ascending, diagonal included):
  * lofC's level-of-fill pattern (src/iluk.cpp:193-334), built row-parallel over
  * `threads` host threads -- level 1 by the original L x U entries, level >= 2

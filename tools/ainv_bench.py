@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Time to solution of the built-in left preconditioners on the bench's system.
+
+The grid side, restart, tolerance, iteration limit and division mode are
+bench.py's own argument defaults, imported (bench.parse()); the system and the
+right-hand side are formed by the two calls bench.py's main() makes inline
+(laplacian_5pt(grid), rhs_ones(A)), which cannot be imported and are repeated
+here.  One JSON line per preconditioner -- ILU(0) under the bench's
+division mode, AINV at the reference's drop tolerance 0.1, DIAG, NONE -- with
+  setup_s       wall seconds of the gg_set_precond_* call
+  status, iters the solve's return code and iteration count
+  solve_ms      device time of one solve (median of --solves)
+  apply_us      one preconditioner application (gg_time_precond)
+  hbm_frac      gg_bytes_precond / apply time / the HBM peak bench.py uses
+  AINV only: nnz_z, nnz_wt, fused (a one-launch kernel served the apply)
+
+  python tools/ainv_bench.py [--grid 1000] [--solves 3] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def bench_defaults():
+    """bench.py's argument defaults (grid, restart, tol, max_iter, division)"""
+    import bench
+    argv, sys.argv = sys.argv, [sys.argv[0]]
+    try:
+        return bench, bench.parse()
+    finally:
+        sys.argv = argv
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--grid", type=int, default=None, help="grid side (default: bench.py's)")
+    p.add_argument("--solves", type=int, default=3)
+    p.add_argument("--reps", type=int, default=50, help="applications per gg_time_precond call")
+    p.add_argument("--drop-tol", type=float, default=0.1)
+    p.add_argument("--only", default="ilu0,ainv,diag,none")
+    p.add_argument("--out", default=None, help="also append the lines to this file")
+    a = p.parse_args()
+    bench, d = bench_defaults()
+    import ggmres
+    from ggmres import matrices as M
+
+    grid = a.grid or d.grid
+    A = M.laplacian_5pt(grid)              # bench.py main(): the C2 system
+    b = M.rhs_ones(A)
+    n = A.shape[0]
+    lines = []
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        lines.append(line)
+
+    s = ggmres.Solver(0)
+    s.set_matrix(A)
+    setters = {
+        "ilu0": lambda: (s.set_precond_ilu0(), s.set_division(bench.DIV_MODES[d.division])),
+        "ainv": lambda: s.set_precond_ainv(a.drop_tol),
+        "diag": s.set_precond_diag,
+        "none": s.set_precond_none,
+    }
+    for kind in [k for k in a.only.split(",") if k]:
+        t0 = time.perf_counter()
+        setters[kind]()
+        setup = time.perf_counter() - t0
+        ms, g = [], None
+        for _ in range(max(1, a.solves)):
+            g = s.solve(b, restart=d.restart, max_iter=d.max_iter, tol=d.tol)
+            ms.append(g["solve_ms"])
+            if g["ret"] != 0:
+                break                      # not converged: one run of the iteration limit is enough
+        rec = {"precond": kind, "n": n, "grid": grid, "restart": d.restart, "tol": d.tol, "max_iter": d.max_iter,
+               "setup_s": round(setup, 4), "status": g["ret"], "iters": g["iters"], "relres": g["relres"],
+               "solve_ms": round(statistics.median(ms), 4), "solves": len(ms)}
+        if kind != "none":
+            us = s.time_precond(a.reps) * 1e3
+            rec["apply_us"] = round(us, 3)
+            rec["hbm_frac"] = round(s.bytes_precond() / (us * 1e-6) / (bench.HBM_PEAK_GBS * 1e9), 4)
+        if kind == "ilu0":
+            rec["division"] = d.division
+        if kind == "ainv":
+            rec["drop_tol"] = a.drop_tol
+            rec["nnz_z"], rec["nnz_wt"] = s.ainv_nnz()
+            rec["fused"] = s.ainv_fused
+        emit(rec)
+    s.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
