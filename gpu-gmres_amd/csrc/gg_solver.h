@@ -18,6 +18,23 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
                 const gg_options *opt, gg_result *res);
 bool batch_engine_on(gg_solver *s);
 long long batch_history(gg_solver *s, int q, double *out, long long cap);
+// cg.hip: the GG_SOLVE_CG engine behind solve_device (arguments checked by the
+// caller, s->shared set) and the release of its pinned slots (gg_destroy)
+int solve_cg(gg_solver *s, const double *d_b, double *d_x, const gg_options *opt, gg_result *res);
+void cg_release(gg_solver *s);
+// solver.hip, shared with cg.hip.  Fallback: a wavefront solve asked for a
+// repeat on its safe path (the error word's bits 1 and 3); solve_device applies
+// it and starts the solve over
+struct Fallback {
+    int bits;
+};
+void ensure_vectors(gg_solver *s);                // the Ppad-long work vectors, partials, control block, error word
+void apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i = -1);   // out = M in
+void reset_wave(DevTri *T, hipStream_t st);
+void check_err(gg_solver *s);
+int prof_begin(gg_solver *s, int kind, int i);
+void prof_end(gg_solver *s, int mark);
+void prof_collect(gg_solver *s, int executed, size_t upto = (size_t)-1);
 }  // namespace gg
 
 using gg::Csr;
@@ -77,6 +94,7 @@ struct gg_solver {
 
     // workspace
     int m_alloc = -1;
+    bool vec_ok = false;  // the work vectors below are allocated for this space (ensure_vectors)
     DBuf<double> V, w, ww, r, rr, bb, t1, t2, z, xv, bv, y;
     DBuf<double> partA, partB, H, s, cs, sn, ysm;
     // persistent Arnoldi orthogonalization (kernels.hip k_arnoldi_persist)
@@ -96,6 +114,14 @@ struct gg_solver {
     std::vector<size_t> mark_ends;      // marks.size() after each enqueued cycle (pipelined)
     int resid_fallbacks = 0;            // cycles rerun after a persistent grid was not co-resident
     int iter_hint = 0;                  // transient loop: the previous step's inner iterations (0: none)
+    // GG_SOLVE_CG (cg.hip): control block, the dots' block partials (p.q | r.z, z.z),
+    // two pinned slots for the chunk loop's read-backs
+    DBuf<gg::CgState> cgs;
+    DBuf<double> cg_part;
+    gg::CgState *cg_state[2] = {nullptr, nullptr};
+    int *cg_err[2] = {nullptr, nullptr};
+    hipEvent_t cg_ev[2] = {nullptr, nullptr};
+    bool last_cg = false;               // the last solve ran CG (gg_mgs_kernel: no orthogonalization)
     // transient tap-node statistics (gg_transient_set_taps / _get_taps)
     std::vector<int> taps;
     std::vector<double> tap_max, tap_min, tap_avg;

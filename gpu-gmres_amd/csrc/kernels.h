@@ -323,6 +323,37 @@ void launch_update(Gate g, int m, DevState *ds, const double *H, const double *s
                    const UnitMap &um = UnitMap{});
 void launch_end_cycle(const double *part, int G, DevState *ds, double *hist, hipStream_t st);
 
+// ---- conjugate gradients (GG_SOLVE_CG, cg.hip) -------------------------------
+// Device-side control block of a CG solve.  Every launch of an iteration is
+// gated on `done` (any bit) and on it < max_iter, so iterations enqueued past
+// the end of the solve do nothing.
+struct CgState {
+    double normb, resid, tol;
+    double alpha;       // the last step length (diagnostics)
+    double rz[2];       // r . z entering iteration it at rz[it & 1]
+    int done;           // CG_* bits
+    int it;             // iterations performed
+    int max_iter;
+    int pad;
+};
+constexpr int CG_CONV = 1, CG_BREAKDOWN = 2, CG_INIT = 4;
+// With G = the reduction grid, part arrays of 2 G doubles, it = the iteration's
+// 0-based index:
+//   normb = sqrt(sum of part) (0 -> 1)
+void launch_cg_normb(const double *part, int G, CgState *cs, hipStream_t st);
+//   part = block partials of p . q
+void launch_cg_pq(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, hipStream_t st);
+//   pq = sum of part; not pq > 0: CG_BREAKDOWN; alpha = rz / pq; x = alpha p + x; r = (-alpha) q + r
+void launch_cg_xr(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
+                  const double *q, long long Ppad, hipStream_t st);
+//   part = block partials of r . z, then of z . z
+void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, hipStream_t st);
+//   rzn, zz = sums of part; resid = hist[it + 1] = sqrt(zz) / normb; resid < tol: CG_CONV; else not
+//   rzn > 0: CG_BREAKDOWN; else p = (rzn / rz) p + z.  start (the initial residual, nothing
+//   counted): hist[0], resid <= tol: CG_INIT, p = z
+void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
+                 double *hist, long long Ppad, hipStream_t st);
+
 // ---- batched (many-RHS) launches, kernels.hip: nsc scenarios per launch,
 // scenario q's per-scenario buffers (vectors, partials, H, Givens, history,
 // control block, hand-off granules) q * zs bytes after scenario 0's; the gate's

@@ -5118,6 +5118,191 @@ __global__ void k_end_cycle(const double *part, int G, DevState *ds, double *his
     }
 }
 
+// ================================================================ CG kernels
+// Left-preconditioned conjugate gradients (cg.hip; DESIGN.md "CG").  Besides
+// the SpMV and the preconditioner an iteration is four launches, each in
+// k_mgs_step's form: the previous launch's G partials summed redundantly in
+// every block (sum_partials: the same bits everywhere), the scalar formed,
+// the vectors streamed kUnroll 16-B units per stream in flight, partials left
+// for the next launch.  Every dot keeps k_dot's order (thread t of block b:
+// units b*256 + t + j*G*256 ascending, block_sum's tree).  No atomics; the
+// control block is written by thread 0 of block 0 alone, and a word a launch
+// writes is read by no other block of that launch except the done bits -- a
+// block that sees them early returns where it would have returned anyway
+// (every block forms the same scalars).  rz alternates between two words: the
+// launch that forms iteration it's beta from rz[it & 1] stores the next one.
+__global__ void k_cg_normb(const double *part, int G, CgState *cs)
+{
+    const double s = sum_partials(part, G);
+    if (threadIdx.x == 0) {
+        const double nb = sqrt(s);
+        cs->normb = (nb == 0.0) ? 1.0 : nb;
+    }
+}
+
+// block partials of p . q
+__global__ __launch_bounds__(kBlock) void k_cg_pq(Gate g, const double *__restrict__ p,
+                                                  const double *__restrict__ q, double *part, long long units)
+{
+    if (gated(g)) return;
+    double acc = 0.0;
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x; u0 < units; u0 += kUnroll * stride) {
+        double2 a[kUnroll], b[kUnroll];
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            const long long u = u0 + j * stride;
+            if (u < units) { a[j] = ld2(p, u); b[j] = ld2(q, u); }
+        }
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            if (u0 + j * stride < units) {
+                acc += a[j].x * b[j].x;
+                acc += a[j].y * b[j].y;
+            }
+        }
+    }
+    acc = block_sum(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// pq from the partials; alpha = rz / pq (breakdown unless pq > 0, NaN included);
+// x = alpha p + x;  r = (-alpha) q + r
+__global__ __launch_bounds__(kBlock) void k_cg_xr(Gate g, int it, CgState *cs, const double *part, int G,
+                                                  double *__restrict__ x, const double *__restrict__ p,
+                                                  double *__restrict__ r, const double *__restrict__ q,
+                                                  long long units)
+{
+    if (gated(g)) return;
+    const long long stride = (long long)gridDim.x * kBlock;
+    long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
+    double2 xv[kUnroll], pv[kUnroll], rv[kUnroll], qv[kUnroll];
+    auto load = [&]() {
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            const long long u = u0 + j * stride;
+            if (u < units) {
+                xv[j] = ld2(x, u);
+                pv[j] = ld2(p, u);
+                rv[j] = ld2(r, u);
+                qv[j] = ld2(q, u);
+            }
+        }
+    };
+    load();                 // the first chunk is in flight while pq is summed
+    const double pq = sum_partials(part, G);
+    const double rz = cs->rz[it & 1];
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (!(pq > 0.0)) {
+        if (first) cs->done = CG_BREAKDOWN;
+        return;
+    }
+    const double alpha = rz / pq;
+    if (first) cs->alpha = alpha;
+    const double na = -alpha;
+    while (u0 < units) {
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            const long long u = u0 + j * stride;
+            if (u < units) {
+                xv[j].x = alpha * pv[j].x + xv[j].x;
+                xv[j].y = alpha * pv[j].y + xv[j].y;
+                rv[j].x = na * qv[j].x + rv[j].x;
+                rv[j].y = na * qv[j].y + rv[j].y;
+                st2(x, u, xv[j]);
+                st2(r, u, rv[j]);
+            }
+        }
+        u0 += kUnroll * stride;
+        load();
+    }
+}
+
+// block partials of r . z (part[b]) and z . z (part[G + b]) in one pass
+__global__ __launch_bounds__(kBlock) void k_cg_rz(Gate g, const double *__restrict__ r,
+                                                  const double *__restrict__ z, double *part, long long units)
+{
+    if (gated(g)) return;
+    double acc[2] = {0.0, 0.0};
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x; u0 < units; u0 += kUnroll * stride) {
+        double2 a[kUnroll], b[kUnroll];
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            const long long u = u0 + j * stride;
+            if (u < units) { a[j] = ld2(r, u); b[j] = ld2(z, u); }
+        }
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            if (u0 + j * stride < units) {
+                acc[0] += a[j].x * b[j].x;
+                acc[0] += a[j].y * b[j].y;
+                acc[1] += b[j].x * b[j].x;
+                acc[1] += b[j].y * b[j].y;
+            }
+        }
+    }
+    block_sum_store<2>(acc, 2, part + blockIdx.x, gridDim.x);
+}
+
+// rzn, zz from the partials; res = sqrt(zz) / normb into the history; converged
+// (START: res <= tol, else res < tol), breakdown (not converged and not rzn > 0,
+// NaN included); otherwise p = beta p + z with beta = rzn / rz (START: p = z).
+// it: the iteration's 0-based index (START: the initial residual, nothing counted)
+template <bool START>
+__global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, const double *part, int G,
+                                                 double *__restrict__ p, const double *__restrict__ z,
+                                                 double *hist, long long units)
+{
+    if (gated(g)) return;
+    const long long stride = (long long)gridDim.x * kBlock;
+    long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
+    double2 pv[kUnroll], zv[kUnroll];
+    auto load = [&]() {
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            const long long u = u0 + j * stride;
+            if (u < units) {
+                zv[j] = ld2(z, u);
+                if (!START) pv[j] = ld2(p, u);
+            }
+        }
+    };
+    load();
+    const double rzn = sum_partials(part, G);
+    const double zz = sum_partials(part + G, G);
+    const double res = sqrt(zz) / cs->normb;
+    const bool conv = START ? res <= cs->tol : res < cs->tol;
+    const bool brk = !conv && !(rzn > 0.0);
+    const int done_it = START ? 0 : it + 1;            // iterations performed
+    const double rz = START ? 0.0 : cs->rz[it & 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        cs->resid = res;
+        hist[done_it] = res;
+        cs->it = done_it;
+        cs->rz[done_it & 1] = rzn;
+        if (conv) cs->done = START ? CG_INIT : CG_CONV;
+        else if (brk) cs->done = CG_BREAKDOWN;
+    }
+    if (conv || brk) return;
+    const double beta = START ? 0.0 : rzn / rz;
+    while (u0 < units) {
+#pragma unroll
+        for (int j = 0; j < kUnroll; j++) {
+            const long long u = u0 + j * stride;
+            if (u < units) {
+                if (!START) {
+                    zv[j].x = beta * pv[j].x + zv[j].x;
+                    zv[j].y = beta * pv[j].y + zv[j].y;
+                }
+                st2(p, u, zv[j]);
+            }
+        }
+        u0 += kUnroll * stride;
+        load();
+    }
+}
+
 inline int blocks_for(long long n, int bs = kBlock, int cap = 65535)
 {
     long long b = (n + bs - 1) / bs;
@@ -6267,6 +6452,31 @@ void launch_update_b(Gate g, int m, DevState *ds, const double *H, const double 
 void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, int nsc, long long zs, hipStream_t st)
 {
     k_end_cycle<<<dim3(1, nsc), kBlock, 0, st>>>(part, G, ds, hist, zs);
+}
+
+// ---- CG (cg.hip) ----------------------------------------------------------------
+void launch_cg_normb(const double *part, int G, CgState *cs, hipStream_t st)
+{
+    k_cg_normb<<<1, kBlock, 0, st>>>(part, G, cs);
+}
+void launch_cg_pq(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, hipStream_t st)
+{
+    k_cg_pq<<<G, kBlock, 0, st>>>(g, p, q, part, Ppad / 2);
+}
+void launch_cg_xr(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
+                  const double *q, long long Ppad, hipStream_t st)
+{
+    k_cg_xr<<<G, kBlock, 0, st>>>(g, it, cs, part, G, x, p, r, q, Ppad / 2);
+}
+void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, hipStream_t st)
+{
+    k_cg_rz<<<G, kBlock, 0, st>>>(g, r, z, part, Ppad / 2);
+}
+void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
+                 double *hist, long long Ppad, hipStream_t st)
+{
+    if (start) k_cg_p<true><<<G, kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2);
+    else k_cg_p<false><<<G, kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2);
 }
 
 }  // namespace gg

@@ -758,14 +758,16 @@ void setup_space(gg_solver *s, const Wave2D *wl, const int *prow = nullptr, cons
         s->dA.upload(Ap, s->st);
     }
     s->m_alloc = -1;   // workspace follows the space
+    s->vec_ok = false;
 }
 
-void ensure_workspace(gg_solver *s, int m)
+}  // namespace
+
+// the work vectors alone (cg.hip needs no Krylov basis; ensure_workspace adds it)
+void gg::ensure_vectors(gg_solver *s)
 {
-    if (s->m_alloc == m) return;
+    if (s->vec_ok) return;
     const long long P = s->Ppad;
-    s->V.alloc((size_t)(m + 1) * P);
-    GG_HIP(hipMemsetAsync(s->V.p, 0, (size_t)(m + 1) * P * sizeof(double), s->st));
     for (DBuf<double> *b : {&s->w, &s->ww, &s->r, &s->rr, &s->bb, &s->t1, &s->t2, &s->z, &s->xv,
                             &s->bv, &s->y}) {
         b->alloc(P);
@@ -773,6 +775,21 @@ void ensure_workspace(gg_solver *s, int m)
     }
     s->partA.alloc(1024);
     s->partB.alloc(1024);
+    if (!s->ds.p) s->ds.alloc(1);
+    if (!s->err.p) s->err.alloc(1);
+    s->vec_ok = true;
+}
+
+namespace {
+
+void ensure_workspace(gg_solver *s, int m)
+{
+    if (s->m_alloc == m) return;
+    const long long P = s->Ppad;
+    s->V.alloc((size_t)(m + 1) * P);
+    GG_HIP(hipMemsetAsync(s->V.p, 0, (size_t)(m + 1) * P * sizeof(double), s->st));
+    s->vec_ok = false;      // a new basis comes with new, zeroed work vectors
+    ensure_vectors(s);
     {
         const char *e = std::getenv("GG_NO_PERSIST");
         const bool off = e && e[0] == '1';
@@ -798,13 +815,8 @@ void ensure_workspace(gg_solver *s, int m)
     s->cs.alloc(m + 1);
     s->sn.alloc(m + 1);
     s->ysm.alloc(m + 1);
-    if (!s->ds.p) s->ds.alloc(1);
-    if (!s->err.p) s->err.alloc(1);
     s->m_alloc = m;
 }
-
-int prof_begin(gg_solver *s, int kind, int i);
-void prof_end(gg_solver *s, int mark);
 
 // one triangular solve, bracketed for in-solve timing when `i` >= 0
 void trsv(gg_solver *s, Gate g, DevTri &T, int kind, int i, const double *in, double *out)
@@ -849,8 +861,10 @@ void apply_user(gg_solver *s, Gate g, int op, const double *in, double *out)
     launch_f32_to_f64(Gate{}, s->fout.p, out, n, s->st);
 }
 
+}  // namespace
+
 // ---- preconditioner operators (enqueue only; graph-capturable) ----------
-void apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i = -1)
+void gg::apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i)
 {
     if (s->pkind == GG_PRECOND_USER) {
         apply_user(s, g, GG_APPLY_MINV, in, out);
@@ -877,6 +891,9 @@ void apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i = -1)
     trsv(s, g, s->L, GG_PROF_TRSV_L, i, in, s->t1.p);
     trsv(s, g, s->U, GG_PROF_TRSV_U, i, s->t1.p, out);
 }
+
+namespace {
+
 // Split engine (see gg_solver): every operand in layout space.
 // Ml(v) = L^-1 P_r D_l^-1 v (DevPrecond_left, src/preconditioner.cu:1592-1626),
 // `in` already in A' row order (b, or nothing: the SpMV folds it, spmv_left)
@@ -964,13 +981,15 @@ int prof_event(gg_solver *s)
     GG_HIP(hipEventRecord(s->prof_pool[idx], s->st));
     return idx;
 }
-int prof_begin(gg_solver *s, int kind, int i)
+}  // namespace
+
+int gg::prof_begin(gg_solver *s, int kind, int i)
 {
     if (!((s->prof_mask >> kind) & 1)) return -1;
     s->marks.push_back({kind, i, prof_event(s), -1});
     return (int)s->marks.size() - 1;
 }
-void prof_end(gg_solver *s, int mark)
+void gg::prof_end(gg_solver *s, int mark)
 {
     if (mark < 0) return;
     s->marks[mark].e1 = prof_event(s);
@@ -978,7 +997,7 @@ void prof_end(gg_solver *s, int mark)
 // after a cycle has completed: account marks of iterations that really ran
 // (the first `upto` marks -- the pipelined loop keeps the next cycle's, whose
 // events are still pending; the pool is reused once no mark is left)
-void prof_collect(gg_solver *s, int executed, size_t upto = (size_t)-1)
+void gg::prof_collect(gg_solver *s, int executed, size_t upto)
 {
     if (!s->prof_mask) {
         s->marks.clear();
@@ -1005,6 +1024,8 @@ void prof_collect(gg_solver *s, int executed, size_t upto = (size_t)-1)
         s->prof_free.clear();
     }
 }
+
+namespace {
 
 // ---- GMRES phases ------------------------------------------------------------
 void enqueue_init(gg_solver *s)
@@ -1269,8 +1290,10 @@ void enqueue_cycle(gg_solver *s, int m, int i0 = 0, int i1 = -1, bool tail = tru
 }
 
 
+}  // namespace
+
 // re-arm a wavefront triangle's hand-off state (granules, 3D progress words)
-void reset_wave(DevTri *T, hipStream_t st)
+void gg::reset_wave(DevTri *T, hipStream_t st)
 {
     launch_fill_u64(T->bnd.p, T->wl.ngran(), kSentinel, st);
     if (T->wl.tile)     // the tile kernel's task queue (a launch cut short would leave it armed)
@@ -1283,11 +1306,8 @@ void reset_wave(DevTri *T, hipStream_t st)
 // WD_RCP step saw a numerator outside its safe range (repeat with WD_HW), bit
 // 3 = a statically dealt tile grid was not co-resident (repeat with the tile
 // queue, k_trsv_tile3d).  Bits 1 and 3 throw Fallback: the caller applies it
-// (apply_fallback) and repeats the solve / apply.
-struct Fallback {
-    int bits;
-};
-void check_err(gg_solver *s)
+// (apply_fallback) and repeats the solve / apply.  (struct Fallback: gg_solver.h)
+void gg::check_err(gg_solver *s)
 {
     // on the solver's stream: a plain hipMemcpy would not wait for its kernels
     int err = 0;
@@ -1297,6 +1317,9 @@ void check_err(gg_solver *s)
     GG_REQUIRE((err & 1) == 0, GG_ETIMEOUT, "wavefront triangular solve: boundary wait timed out");
     if (err & 2) throw Fallback{err};
 }
+
+namespace {
+
 // the control block and the error word in one round trip (after a cycle)
 DevState read_state_checked(gg_solver *s)
 {
@@ -1354,9 +1377,13 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
     const int m = opt->restart;
     GG_REQUIRE(m >= 1 && m <= 512, GG_EINVAL, "gg_solve: restart must be in [1, 512]");
     GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, "gg_solve: negative max_iter");
-    GG_REQUIRE((opt->flags & ~GG_SOLVE_SHARED_DEVICE) == 0, GG_EINVAL,
+    GG_REQUIRE((opt->flags & ~(GG_SOLVE_SHARED_DEVICE | GG_SOLVE_CG)) == 0, GG_EINVAL,
                (opt->flags & GG_SOLVE_CGS2) ? "gg_solve: GG_SOLVE_CGS2 is a sharded-solve (gg_dd_solve) mode"
                                             : "gg_solve: unknown flags");
+    const bool cg = (opt->flags & GG_SOLVE_CG) != 0;
+    GG_REQUIRE(!cg || (s->pkind != GG_PRECOND_SPLIT && !user_kind(s)), GG_EINVAL,
+               "gg_solve: GG_SOLVE_CG takes a left preconditioner built by the library (NONE, DIAG, AINV, "
+               "ILU0, ILUK, LU), not the split or caller-supplied ones");
     s->shared = (opt->flags & GG_SOLVE_SHARED_DEVICE) != 0;
     if (s->shared) {
         // only kernels whose workgroups wait on earlier-dispatched ones
@@ -1370,6 +1397,8 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
     }
     const int n = s->A.n;
     set_device(s);
+    s->last_cg = cg;
+    if (cg) return solve_cg(s, d_b, d_x, opt, res);      // cg.hip
     ensure_workspace(s, m);
     const long long need = (long long)opt->max_iter + opt->max_iter / m + 4;
     if (need > s->hist_cap) {
@@ -1664,6 +1693,7 @@ const char *gg_strerror(int status)
     case GG_ESTATE: return "invalid call order";
     case GG_ETIMEOUT: return "device wait timed out";
     case GG_ECOMM: return "communication error";
+    case GG_EBREAKDOWN: return "conjugate gradients broke down (matrix or preconditioner not positive definite)";
     default: return "unknown status";
     }
 }
@@ -1705,6 +1735,7 @@ int gg_destroy(gg_solver *s)
     for (hipEvent_t e : s->prof_pool) (void)hipEventDestroy(e);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     gg::batch_release(s);
+    gg::cg_release(s);
     if (s->h_state) (void)hipHostFree(s->h_state);
     if (s->h_err) (void)hipHostFree(s->h_err);
     for (int k = 0; k < 2; k++) {
@@ -2241,7 +2272,7 @@ int gg_mgs_kernel(gg_solver *s, char *name, int cap)
 {
     if (!s || !name || cap <= 0) return GG_EINVAL;
     std::string k;
-    if (s->m_alloc > 0 && !s->shared) {
+    if (s->m_alloc > 0 && !s->shared && !s->last_cg) {
         if (s->persist)
             k = "k_arnoldi_persist<" + std::to_string(arnoldi_persist_units(s->G, s->Ppad)) + ", " +
                 std::to_string(mgs_gather_form()) + ", " + std::to_string(mgs_prefetch()) + ">";

@@ -15,11 +15,13 @@ PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("GGMRES_LIB") or os.path.join(PKG_ROOT, "lib", "libggmres.so")
 
 GG_OK, GG_NOT_CONVERGED = 0, 1
+EBREAKDOWN = -8               # gg_status GG_EBREAKDOWN: a SOLVE_CG solve met p.Ap or r.Mr not > 0
 PRECOND_NONE, PRECOND_ILU0, PRECOND_ILUK, PRECOND_LU, PRECOND_SPLIT, PRECOND_USER, PRECOND_USER_SPLIT = range(7)
 PRECOND_AINV, PRECOND_DIAG = 7, 8
 APPLY_MINV, APPLY_LEFT, APPLY_RIGHT, APPLY_START, APPLY_RHS = range(5)
 SOLVE_SHARED_DEVICE = 0x1     # gg_options.flags: other solvers share the device (ggmres.h)
 SOLVE_CGS2 = 0x2              # gg_options.flags: CGS2 orthogonalization (sharded solve only)
+SOLVE_CG = 0x4                # gg_options.flags: preconditioned conjugate gradients (A and M SPD; ggmres.h)
 
 # every symbol include/ggmres.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -162,6 +164,10 @@ def lib():
 
 
 def _check(rc, allow_nc=False):
+    """allow_nc: the statuses a solve reports beside its result pass through --
+    GG_NOT_CONVERGED and EBREAKDOWN (x is the last iterate)"""
+    if allow_nc and rc == EBREAKDOWN:
+        return rc
     if rc < 0 or (rc == GG_NOT_CONVERGED and not allow_nc):
         raise GGError(rc, lib().gg_last_error().decode())
     return rc
@@ -383,14 +389,14 @@ class Solver:
                     restarts=[r.restarts for r in res], relres=[r.relres for r in res],
                     status=[r.status for r in res], solve_ms=res[0].solve_ms if len(res) else 0.0)
 
-    def solve_batch(self, B, X0=None, restart=30, max_iter=3000, tol=1e-10):
+    def solve_batch(self, B, X0=None, restart=30, max_iter=3000, tol=1e-10, flags=0):
         """nrhs independent solves A x_q = b_q (rows of B), batched; returns
         dict(x [nrhs, n], iters / inner / restarts / relres / status per
         scenario, hist = per-scenario histories)."""
         B = np.ascontiguousarray(np.atleast_2d(B), np.float64)
         S, n = B.shape
         X = np.zeros((S, n)) if X0 is None else np.array(np.atleast_2d(X0), np.float64, copy=True, order="C")
-        o = Options(int(restart), int(max_iter), float(tol), 0)
+        o = Options(int(restart), int(max_iter), float(tol), int(flags))     # (the batch defines no flags)
         res = (Result * S)()
         rc = _check(lib().gg_solve_batch(self.h, S, B.reshape(-1), n, X.reshape(-1), n, ctypes.byref(o), res),
                     allow_nc=True)
@@ -622,6 +628,13 @@ class Solver:
         G = ctypes.c_int()
         _check(lib().gg_reduce_blocks(self.h, ctypes.byref(G)))     # the solver's own s->G
         return out, G.value
+
+    @property
+    def reduce_blocks(self):
+        """G, the block partials of every dot in the solver's vector space (gg_reduce_blocks)"""
+        G = ctypes.c_int()
+        _check(lib().gg_reduce_blocks(self.h, ctypes.byref(G)))
+        return G.value
 
     def profile_select(self, kinds):
         """Switch the timed families to `kinds` WITHOUT clearing what was

@@ -53,7 +53,8 @@ enum gg_status {
     GG_ENOMEM = -4,        /* device allocation failed                     */
     GG_ESTATE = -5,        /* call order (e.g. solve before set_matrix)    */
     GG_ETIMEOUT = -6,      /* a device-side wait exceeded its spin bound   */
-    GG_ECOMM = -7          /* RCCL / multi-GPU error                       */
+    GG_ECOMM = -7,         /* RCCL / multi-GPU error                       */
+    GG_EBREAKDOWN = -8     /* GG_SOLVE_CG: p.Ap or r.Mr not positive       */
 };
 
 enum gg_precond_kind {
@@ -107,6 +108,30 @@ typedef struct gg_options {
  * different rounding (north_star's 1e-10 history tolerance); the default
  * stays MGS.  gg_solve refuses it (GG_EINVAL). */
 #define GG_SOLVE_CGS2 0x2
+/* gg_options.flags: solve by left-preconditioned conjugate gradients instead
+ * of GMRES(m).  A and the preconditioner M are ASSUMED symmetric positive
+ * definite -- the library cannot observe it, the caller states it.  A
+ * numerical choice like the preconditioner kind, not a faster path to the same
+ * numbers: no Krylov basis, no orthogonalization, no restarts.
+ *   bb = M b; normb = ||bb|| (0 -> 1); r = b - A x; z = M r; p = z; rz = r.z
+ *   repeat: q = A p; alpha = rz / p.q; x = alpha p + x; r = (-alpha) q + r;
+ *           z = M r; rzn = r.z; resid = ||z|| / normb; beta = rzn / rz;
+ *           p = beta p + z; rz = rzn
+ * opt->tol keeps its meaning (||M r|| / ||M b||, "<=" on the initial residual,
+ * "<" afterwards); opt->max_iter bounds the CG iterations; opt->restart is
+ * validated and otherwise ignored.  gg_result: iters = inner_iters = the
+ * iterations performed, restarts = 0, relres = the last ||z|| / normb;
+ * gg_get_history: the initial value, then one entry per iteration.
+ * Accepted by gg_solve, gg_solve_device, gg_solve_device_f32 and the
+ * gg_transient* loops (warm start as with GMRES), with GG_PRECOND_NONE, DIAG,
+ * AINV, ILU0, ILUK or LU (host- or device-factored, any triangular-solve
+ * path); GG_EINVAL with GG_PRECOND_SPLIT / USER / USER_SPLIT and in
+ * gg_solve_batch*.  May be combined with GG_SOLVE_SHARED_DEVICE under that
+ * flag's own conditions (the CG kernels wait on nothing).
+ * GG_EBREAKDOWN: p.Ap is not > 0, or r.Mr is not > 0 while the solve has not
+ * converged (NaN counts as not > 0) -- how a matrix or preconditioner that is
+ * not SPD shows.  x then holds the last iterate, res->status the code. */
+#define GG_SOLVE_CG 0x4
 
 typedef struct gg_result {
     int status;        /* GG_OK / GG_NOT_CONVERGED / error                        */
@@ -243,7 +268,8 @@ int gg_division_active(gg_solver *s, int which);
 int gg_trsv_kernel(gg_solver *s, int which, char *name, int cap);
 /* the one-launch orthogonalization kernel of the last solve's inner
  * iterations (k_arnoldi_persist<J> / k_arnoldi_wide), "" when the per-step
- * kernels ran (or before the first solve); returns its length */
+ * kernels ran (before the first solve, or after a GG_SOLVE_CG solve, which
+ * orthogonalizes nothing); returns its length */
 int gg_mgs_kernel(gg_solver *s, char *name, int cap);
 /* the dependency chain of triangle `which` (0 = L / Ml, 1 = U / Mr): its
  * level count (the dataflow solve), or the wavefront's critical steps
@@ -294,7 +320,8 @@ int gg_device_fingerprint(const void *const *d_p, const unsigned long long *byte
  * cache, compat/engine_abi.cpp) */
 long long gg_set_matrix_count(void);
 /* residual history of the last solve: [beta0/normb, |s[i+1]|/normb per inner
- * iteration, beta/normb after each restart ...] in event order.  Returns the
+ * iteration, beta/normb after each restart ...] in event order (GG_SOLVE_CG:
+ * the initial ||M r||/normb, then one entry per iteration).  Returns the
  * number of entries (may exceed cap; only cap are written). */
 int gg_get_history(gg_solver *s, double *out, int cap);
 

@@ -14,7 +14,15 @@ division mode, AINV at the reference's drop tolerance 0.1, DIAG, NONE -- with
   hbm_frac      gg_bytes_precond / apply time / the HBM peak bench.py uses
   AINV only: nnz_z, nnz_wt, fused (a one-launch kernel served the apply)
 
-  python tools/ainv_bench.py [--grid 1000] [--solves 3] [--out FILE]
+--cg: GMRES(restart) and preconditioned CG (GG_SOLVE_CG; the system is SPD)
+side by side instead -- per preconditioner one warm-up solve of each, then
+--solves (default 5 here) timed solves of each, alternating in this process;
+one JSON line with, for "gmres" and "cg": status, iters, relres, solve_ms (the
+median of the device-event times), us_per_iter, solves; and cg_speedup =
+gmres solve_ms / cg solve_ms.  A method that does not converge within the
+iteration limit is timed once.
+
+  python tools/ainv_bench.py [--grid 1000] [--solves 3] [--cg] [--out FILE]
 """
 import argparse
 import json
@@ -37,15 +45,43 @@ def bench_defaults():
         sys.argv = argv
 
 
+def side_by_side(s, ggmres, b, kind, n, grid, d, setup, solves):
+    """GMRES(restart) and CG alternating on solver s after one warm-up of each"""
+    flags = {"gmres": 0, "cg": ggmres.SOLVE_CG}
+    ms = {k: [] for k in flags}
+    last = {}
+    for k, f in flags.items():                 # warm-up: code objects, work space, the fallbacks
+        last[k] = s.solve(b, restart=d.restart, max_iter=d.max_iter, tol=d.tol, flags=f)
+    for _ in range(solves):
+        for k, f in flags.items():
+            if last[k]["ret"] != 0 and ms[k]:
+                continue                       # not converged: one timed run of the iteration limit is enough
+            last[k] = s.solve(b, restart=d.restart, max_iter=d.max_iter, tol=d.tol, flags=f)
+            ms[k].append(last[k]["solve_ms"])
+    rec = {"precond": kind, "n": n, "grid": grid, "restart": d.restart, "tol": d.tol, "max_iter": d.max_iter,
+           "setup_s": round(setup, 4)}
+    if kind == "ilu0":
+        rec["division"] = d.division
+    for k in flags:
+        g, med = last[k], statistics.median(ms[k])
+        rec[k] = {"status": g["ret"], "iters": g["iters"], "relres": g["relres"], "solve_ms": round(med, 4),
+                  "us_per_iter": round(med * 1e3 / max(g["inner"], 1), 3), "solves": len(ms[k])}
+    rec["cg_speedup"] = round(rec["gmres"]["solve_ms"] / rec["cg"]["solve_ms"], 3)
+    return rec
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--grid", type=int, default=None, help="grid side (default: bench.py's)")
-    p.add_argument("--solves", type=int, default=3)
+    p.add_argument("--solves", type=int, default=None, help="timed solves (default 3; 5 of each method with --cg)")
+    p.add_argument("--cg", action="store_true", help="GMRES(restart) and CG (GG_SOLVE_CG) side by side")
     p.add_argument("--reps", type=int, default=50, help="applications per gg_time_precond call")
     p.add_argument("--drop-tol", type=float, default=0.1)
     p.add_argument("--only", default="ilu0,ainv,diag,none")
     p.add_argument("--out", default=None, help="also append the lines to this file")
     a = p.parse_args()
+    if a.solves is None:
+        a.solves = 5 if a.cg else 3
     bench, d = bench_defaults()
     import ggmres
     from ggmres import matrices as M
@@ -73,6 +109,9 @@ def main():
         t0 = time.perf_counter()
         setters[kind]()
         setup = time.perf_counter() - t0
+        if a.cg:
+            emit(side_by_side(s, ggmres, b, kind, n, grid, d, setup, max(1, a.solves)))
+            continue
         ms, g = [], None
         for _ in range(max(1, a.solves)):
             g = s.solve(b, restart=d.restart, max_iter=d.max_iter, tol=d.tol)
