@@ -22,13 +22,18 @@ long long batch_history(gg_solver *s, int q, double *out, long long cap);
 // caller, s->shared set) and the release of its pinned slots (gg_destroy)
 int solve_cg(gg_solver *s, const double *d_b, double *d_x, const gg_options *opt, gg_result *res);
 void cg_release(gg_solver *s);
-// solver.hip, shared with cg.hip.  Fallback: a wavefront solve asked for a
+// bicgstab.hip: the GG_SOLVE_BICGSTAB engine, likewise
+int solve_bicgstab(gg_solver *s, const double *d_b, double *d_x, const gg_options *opt, gg_result *res);
+void bicgstab_release(gg_solver *s);
+// solver.hip, shared with cg.hip and bicgstab.hip.  Fallback: a wavefront solve asked for a
 // repeat on its safe path (the error word's bits 1 and 3); solve_device applies
 // it and starts the solve over
 struct Fallback {
     int bits;
 };
-void ensure_vectors(gg_solver *s);                // the Ppad-long work vectors, partials, control block, error word
+// the Ppad-long work vectors, partials, control block, error word; bicgstab: also the
+// three vectors that solve alone keeps (bi_rt, bi_t, bi_q)
+void ensure_vectors(gg_solver *s, bool bicgstab = false);
 void apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i = -1);   // out = M in
 void reset_wave(DevTri *T, hipStream_t st);
 void check_err(gg_solver *s);
@@ -121,7 +126,17 @@ struct gg_solver {
     gg::CgState *cg_state[2] = {nullptr, nullptr};
     int *cg_err[2] = {nullptr, nullptr};
     hipEvent_t cg_ev[2] = {nullptr, nullptr};
-    bool last_cg = false;               // the last solve ran CG (gg_mgs_kernel: no orthogonalization)
+    bool last_cg = false;               // the last solve ran CG or BiCGStab (gg_mgs_kernel: no orthogonalization)
+    // GG_SOLVE_BICGSTAB (bicgstab.hip): control block, the dots' block partials
+    // (rt.v | t.s, t.t | r.r, rt.r), the vectors beyond the GMRES work space
+    // (the shadow residual, t, the SpMV output M is applied to), pinned slots
+    DBuf<gg::BiState> bis;
+    DBuf<double> bi_part;
+    DBuf<double> bi_rt, bi_t, bi_q;
+    bool bi_vec_ok = false;
+    gg::BiState *bi_state[2] = {nullptr, nullptr};
+    int *bi_err[2] = {nullptr, nullptr};
+    hipEvent_t bi_ev[2] = {nullptr, nullptr};
     // transient tap-node statistics (gg_transient_set_taps / _get_taps)
     std::vector<int> taps;
     std::vector<double> tap_max, tap_min, tap_avg;

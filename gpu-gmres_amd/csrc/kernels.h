@@ -354,6 +354,40 @@ void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G,
 void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
                  double *hist, long long Ppad, hipStream_t st);
 
+// ---- BiCGStab (GG_SOLVE_BICGSTAB, bicgstab.hip) ------------------------------
+// Device-side control block of a BiCGStab solve, gated like CgState.  alpha
+// and omega are written by one launch and read by later ones; rho alternates
+// like CgState::rz (the launch that reads rho[it & 1] stores rho[(it + 1) & 1]).
+struct BiState {
+    double normb, resid, tol;
+    double alpha, omega;
+    double rho[2];      // rt . r entering iteration it at rho[it & 1]
+    double bad;         // BI_BREAKDOWN: the scalar that was zero or not finite
+    int done;           // BI_* bits
+    int it;             // iterations performed
+    int max_iter;
+    int why;            // BI_BREAKDOWN: which scalar (BI_WHY_*)
+};
+constexpr int BI_CONV = 1, BI_BREAKDOWN = 2, BI_INIT = 4;
+constexpr int BI_WHY_RHO = 1, BI_WHY_RTV = 2, BI_WHY_OMEGA = 3;
+// The two plain dot launches of an iteration are CG's: launch_cg_pq (rt . v)
+// and launch_cg_rz (t . s, then t . t).  it = the iteration's 0-based index.
+//   normb = sqrt(sum of part) (0 -> 1)
+void launch_bi_normb(const double *part, int G, BiState *bs, hipStream_t st);
+//   rtv = sum of part; zero or not finite: BI_BREAKDOWN; alpha = rho / rtv; r = s = (-alpha) v + r
+void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double *r, const double *v,
+                 long long Ppad, hipStream_t st);
+//   ts, tt = sums of part_in; omega = tt > 0 ? ts / tt : 0; x = omega s + (alpha p + x);
+//   r = (-omega) t + s in place of s; part_out = block partials of r . r, then of rt . r
+void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, const double *p, double *s,
+                  const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st);
+//   rr, rhon = sums of part; resid = hist[it + 1] = sqrt(rr) / normb; resid < tol: BI_CONV; else omega or
+//   rhon zero or not finite: BI_BREAKDOWN; else p = ((rhon / rho) (alpha / omega)) ((-omega) v + p) + r.
+//   start (the initial residual, nothing counted; part = partials of r . r alone): hist[0], resid <= tol:
+//   BI_INIT, rho = rr zero or not finite: BI_BREAKDOWN, else rt = p = r
+void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
+                 const double *r, double *rt, double *hist, long long Ppad, hipStream_t st);
+
 // ---- batched (many-RHS) launches, kernels.hip: nsc scenarios per launch,
 // scenario q's per-scenario buffers (vectors, partials, H, Givens, history,
 // control block, hand-off granules) q * zs bytes after scenario 0's; the gate's

@@ -759,15 +759,24 @@ void setup_space(gg_solver *s, const Wave2D *wl, const int *prow = nullptr, cons
     }
     s->m_alloc = -1;   // workspace follows the space
     s->vec_ok = false;
+    s->bi_vec_ok = false;
 }
 
 }  // namespace
 
-// the work vectors alone (cg.hip needs no Krylov basis; ensure_workspace adds it)
-void gg::ensure_vectors(gg_solver *s)
+// the work vectors alone (cg.hip and bicgstab.hip need no Krylov basis; ensure_workspace
+// adds it); bicgstab: also that solve's own three vectors, once per vector space
+void gg::ensure_vectors(gg_solver *s, bool bicgstab)
 {
-    if (s->vec_ok) return;
     const long long P = s->Ppad;
+    if (bicgstab && !s->bi_vec_ok) {
+        for (DBuf<double> *b : {&s->bi_rt, &s->bi_t, &s->bi_q}) {
+            b->alloc(P);
+            GG_HIP(hipMemsetAsync(b->p, 0, P * sizeof(double), s->st));
+        }
+        s->bi_vec_ok = true;
+    }
+    if (s->vec_ok) return;
     for (DBuf<double> *b : {&s->w, &s->ww, &s->r, &s->rr, &s->bb, &s->t1, &s->t2, &s->z, &s->xv,
                             &s->bv, &s->y}) {
         b->alloc(P);
@@ -1377,13 +1386,18 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
     const int m = opt->restart;
     GG_REQUIRE(m >= 1 && m <= 512, GG_EINVAL, "gg_solve: restart must be in [1, 512]");
     GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, "gg_solve: negative max_iter");
-    GG_REQUIRE((opt->flags & ~(GG_SOLVE_SHARED_DEVICE | GG_SOLVE_CG)) == 0, GG_EINVAL,
+    GG_REQUIRE((opt->flags & ~(GG_SOLVE_SHARED_DEVICE | GG_SOLVE_CG | GG_SOLVE_BICGSTAB)) == 0, GG_EINVAL,
                (opt->flags & GG_SOLVE_CGS2) ? "gg_solve: GG_SOLVE_CGS2 is a sharded-solve (gg_dd_solve) mode"
                                             : "gg_solve: unknown flags");
     const bool cg = (opt->flags & GG_SOLVE_CG) != 0;
     GG_REQUIRE(!cg || (s->pkind != GG_PRECOND_SPLIT && !user_kind(s)), GG_EINVAL,
                "gg_solve: GG_SOLVE_CG takes a left preconditioner built by the library (NONE, DIAG, AINV, "
                "ILU0, ILUK, LU), not the split or caller-supplied ones");
+    const bool bicgstab = (opt->flags & GG_SOLVE_BICGSTAB) != 0;
+    GG_REQUIRE(!(cg && bicgstab), GG_EINVAL, "gg_solve: GG_SOLVE_CG and GG_SOLVE_BICGSTAB exclude each other");
+    GG_REQUIRE(!bicgstab || (s->pkind != GG_PRECOND_SPLIT && !user_kind(s)), GG_EINVAL,
+               "gg_solve: GG_SOLVE_BICGSTAB takes a left preconditioner built by the library (NONE, DIAG, "
+               "AINV, ILU0, ILUK, LU), not the split or caller-supplied ones");
     s->shared = (opt->flags & GG_SOLVE_SHARED_DEVICE) != 0;
     if (s->shared) {
         // only kernels whose workgroups wait on earlier-dispatched ones
@@ -1397,8 +1411,9 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
     }
     const int n = s->A.n;
     set_device(s);
-    s->last_cg = cg;
+    s->last_cg = cg || bicgstab;
     if (cg) return solve_cg(s, d_b, d_x, opt, res);      // cg.hip
+    if (bicgstab) return solve_bicgstab(s, d_b, d_x, opt, res);      // bicgstab.hip
     ensure_workspace(s, m);
     const long long need = (long long)opt->max_iter + opt->max_iter / m + 4;
     if (need > s->hist_cap) {
@@ -1693,7 +1708,9 @@ const char *gg_strerror(int status)
     case GG_ESTATE: return "invalid call order";
     case GG_ETIMEOUT: return "device wait timed out";
     case GG_ECOMM: return "communication error";
-    case GG_EBREAKDOWN: return "conjugate gradients broke down (matrix or preconditioner not positive definite)";
+    case GG_EBREAKDOWN:
+        return "the recurrence broke down (GG_SOLVE_CG: matrix or preconditioner not positive definite; "
+               "GG_SOLVE_BICGSTAB: rho, rt.v or omega zero or not finite)";
     default: return "unknown status";
     }
 }
@@ -1736,6 +1753,7 @@ int gg_destroy(gg_solver *s)
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     gg::batch_release(s);
     gg::cg_release(s);
+    gg::bicgstab_release(s);
     if (s->h_state) (void)hipHostFree(s->h_state);
     if (s->h_err) (void)hipHostFree(s->h_err);
     for (int k = 0; k < 2; k++) {

@@ -15,13 +15,15 @@ PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("GGMRES_LIB") or os.path.join(PKG_ROOT, "lib", "libggmres.so")
 
 GG_OK, GG_NOT_CONVERGED = 0, 1
-EBREAKDOWN = -8               # gg_status GG_EBREAKDOWN: a SOLVE_CG solve met p.Ap or r.Mr not > 0
+EBREAKDOWN = -8               # gg_status GG_EBREAKDOWN: SOLVE_CG met p.Ap or r.Mr not > 0; SOLVE_BICGSTAB a
+                              # rho, rt.v or omega that is zero or not finite
 PRECOND_NONE, PRECOND_ILU0, PRECOND_ILUK, PRECOND_LU, PRECOND_SPLIT, PRECOND_USER, PRECOND_USER_SPLIT = range(7)
 PRECOND_AINV, PRECOND_DIAG = 7, 8
 APPLY_MINV, APPLY_LEFT, APPLY_RIGHT, APPLY_START, APPLY_RHS = range(5)
 SOLVE_SHARED_DEVICE = 0x1     # gg_options.flags: other solvers share the device (ggmres.h)
 SOLVE_CGS2 = 0x2              # gg_options.flags: CGS2 orthogonalization (sharded solve only)
 SOLVE_CG = 0x4                # gg_options.flags: preconditioned conjugate gradients (A and M SPD; ggmres.h)
+SOLVE_BICGSTAB = 0x8          # gg_options.flags: preconditioned BiCGStab (nonsymmetric A; ggmres.h)
 
 # every symbol include/ggmres.h declares (checked by tests/test_abi.py)
 EXPORTS = [

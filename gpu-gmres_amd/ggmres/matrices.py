@@ -24,8 +24,10 @@ def _finish(A):
     return A
 
 
-def laplacian_5pt(nx, ny=None, diag=4.0, off=-1.0):
-    """2D 5-point stencil, natural row-major order (row r = j*nx + i)."""
+def laplacian_5pt(nx, ny=None, diag=4.0, off=-1.0, upwind=0.0):
+    """2D 5-point stencil, natural row-major order (row r = j*nx + i).  upwind:
+    the west entry (column r - 1) times 1 + upwind, the east entry times
+    1 - upwind (nonsymmetric; 0 leaves every entry as it was)."""
     ny = nx if ny is None else ny
     n = nx * ny
     r = np.arange(n, dtype=np.int64)
@@ -38,7 +40,8 @@ def laplacian_5pt(nx, ny=None, diag=4.0, off=-1.0):
         ok = (i + di >= 0) & (i + di < nx) & (j + dj >= 0) & (j + dj < ny)
         rows.append(r[ok])
         cols.append(r[ok] + di + dj * nx)
-        vals.append(np.full(int(ok.sum()), off))
+        w = off * (1.0 - di * upwind) if (dj == 0 and upwind != 0.0) else off
+        vals.append(np.full(int(ok.sum()), w))
     A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))),
                       shape=(n, n))
     return _finish(A)

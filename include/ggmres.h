@@ -54,7 +54,9 @@ enum gg_status {
     GG_ESTATE = -5,        /* call order (e.g. solve before set_matrix)    */
     GG_ETIMEOUT = -6,      /* a device-side wait exceeded its spin bound   */
     GG_ECOMM = -7,         /* RCCL / multi-GPU error                       */
-    GG_EBREAKDOWN = -8     /* GG_SOLVE_CG: p.Ap or r.Mr not positive       */
+    GG_EBREAKDOWN = -8     /* GG_SOLVE_CG: p.Ap or r.Mr not positive;
+                            * GG_SOLVE_BICGSTAB: rho, rt.v or omega zero or
+                            * not finite (gg_last_error names the scalar)   */
 };
 
 enum gg_precond_kind {
@@ -132,6 +134,36 @@ typedef struct gg_options {
  * converged (NaN counts as not > 0) -- how a matrix or preconditioner that is
  * not SPD shows.  x then holds the last iterate, res->status the code. */
 #define GG_SOLVE_CG 0x4
+/* gg_options.flags: solve by left-preconditioned BiCGStab, i.e. BiCGStab on
+ * (M A) x = M b, instead of GMRES(m): the short-recurrence solver for systems
+ * that are not symmetric positive definite.  No Krylov basis, no
+ * orthogonalization, no restarts; two products with A and two applications of
+ * M per iteration.  A numerical choice, not a faster path to GMRES's numbers.
+ *   bb = M b; normb = ||bb|| (0 -> 1); r = M (b - A x); rt = r; rho = rt.r; p = r
+ *   repeat: v = M (A p); alpha = rho / rt.v; s = (-alpha) v + r;
+ *           t = M (A s); omega = t.t > 0 ? t.s / t.t : 0;
+ *           x = omega s + (alpha p + x); r = (-omega) t + s;
+ *           resid = ||r|| / normb; rhon = rt.r;
+ *           beta = (rhon / rho) (alpha / omega);
+ *           p = beta ((-omega) v + p) + r; rho = rhon
+ * opt->tol keeps its meaning (||M r|| / ||M b||, "<=" on the initial residual,
+ * "<" afterwards; there is no exit on ||s|| at the half step); opt->max_iter
+ * bounds the iterations, each of them two products with A; opt->restart is
+ * validated and otherwise ignored.  gg_result: iters = inner_iters = the
+ * iterations performed, restarts = 0, relres = the last ||r|| / normb;
+ * gg_get_history: the initial value, then one entry per iteration (not
+ * monotone).
+ * Accepted where GG_SOLVE_CG is -- gg_solve, gg_solve_device,
+ * gg_solve_device_f32 and the gg_transient* loops, with GG_PRECOND_NONE, DIAG,
+ * AINV, ILU0, ILUK or LU on any triangular-solve path and in any division
+ * mode; GG_EINVAL together with GG_SOLVE_CG, with GG_PRECOND_SPLIT / USER /
+ * USER_SPLIT, in gg_solve_batch* and in the sharded solve.  May be combined
+ * with GG_SOLVE_SHARED_DEVICE under that flag's own conditions.
+ * GG_EBREAKDOWN: rho or rt.v is zero or not finite (before anything moved in
+ * that iteration), or omega or the next rho is while the solve has not
+ * converged.  x then holds the last iterate, res->status the code, and
+ * gg_last_error names the scalar and its value. */
+#define GG_SOLVE_BICGSTAB 0x8
 
 typedef struct gg_result {
     int status;        /* GG_OK / GG_NOT_CONVERGED / error                        */
@@ -268,8 +300,8 @@ int gg_division_active(gg_solver *s, int which);
 int gg_trsv_kernel(gg_solver *s, int which, char *name, int cap);
 /* the one-launch orthogonalization kernel of the last solve's inner
  * iterations (k_arnoldi_persist<J> / k_arnoldi_wide), "" when the per-step
- * kernels ran (before the first solve, or after a GG_SOLVE_CG solve, which
- * orthogonalizes nothing); returns its length */
+ * kernels ran (before the first solve, or after a GG_SOLVE_CG or
+ * GG_SOLVE_BICGSTAB solve, which orthogonalize nothing); returns its length */
 int gg_mgs_kernel(gg_solver *s, char *name, int cap);
 /* the dependency chain of triangle `which` (0 = L / Ml, 1 = U / Mr): its
  * level count (the dataflow solve), or the wavefront's critical steps
@@ -320,8 +352,9 @@ int gg_device_fingerprint(const void *const *d_p, const unsigned long long *byte
  * cache, compat/engine_abi.cpp) */
 long long gg_set_matrix_count(void);
 /* residual history of the last solve: [beta0/normb, |s[i+1]|/normb per inner
- * iteration, beta/normb after each restart ...] in event order (GG_SOLVE_CG:
- * the initial ||M r||/normb, then one entry per iteration).  Returns the
+ * iteration, beta/normb after each restart ...] in event order (GG_SOLVE_CG
+ * and GG_SOLVE_BICGSTAB: the initial ||M r||/normb, then one entry per
+ * iteration).  Returns the
  * number of entries (may exceed cap; only cap are written). */
 int gg_get_history(gg_solver *s, double *out, int cap);
 

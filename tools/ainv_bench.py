@@ -22,7 +22,13 @@ median of the device-event times), us_per_iter, solves; and cg_speedup =
 gmres solve_ms / cg solve_ms.  A method that does not converge within the
 iteration limit is timed once.
 
-  python tools/ainv_bench.py [--grid 1000] [--solves 3] [--cg] [--out FILE]
+--bicgstab [--upwind U]: GMRES(restart) and BiCGStab (GG_SOLVE_BICGSTAB) side by
+side in the same way, on laplacian_5pt(grid, upwind=U) (nonsymmetric for U != 0);
+with U = 0 the system is SPD and CG is the third method of the alternation.  The
+line holds "gmres", "bicgstab" (and "cg"), bicgstab_speedup = gmres solve_ms /
+bicgstab solve_ms and, with CG, bicgstab_over_cg_us_per_iter.
+
+  python tools/ainv_bench.py [--grid 1000] [--solves 3] [--cg | --bicgstab [--upwind U]] [--out FILE]
 """
 import argparse
 import json
@@ -45,9 +51,9 @@ def bench_defaults():
         sys.argv = argv
 
 
-def side_by_side(s, ggmres, b, kind, n, grid, d, setup, solves):
-    """GMRES(restart) and CG alternating on solver s after one warm-up of each"""
-    flags = {"gmres": 0, "cg": ggmres.SOLVE_CG}
+def side_by_side(s, flags, b, kind, n, grid, d, setup, solves, upwind=None):
+    """the methods of `flags` (name -> gg_options.flags) alternating on solver s
+    after one warm-up of each"""
     ms = {k: [] for k in flags}
     last = {}
     for k, f in flags.items():                 # warm-up: code objects, work space, the fallbacks
@@ -60,34 +66,50 @@ def side_by_side(s, ggmres, b, kind, n, grid, d, setup, solves):
             ms[k].append(last[k]["solve_ms"])
     rec = {"precond": kind, "n": n, "grid": grid, "restart": d.restart, "tol": d.tol, "max_iter": d.max_iter,
            "setup_s": round(setup, 4)}
+    if upwind is not None:
+        rec["upwind"] = upwind
     if kind == "ilu0":
         rec["division"] = d.division
     for k in flags:
         g, med = last[k], statistics.median(ms[k])
         rec[k] = {"status": g["ret"], "iters": g["iters"], "relres": g["relres"], "solve_ms": round(med, 4),
                   "us_per_iter": round(med * 1e3 / max(g["inner"], 1), 3), "solves": len(ms[k])}
-    rec["cg_speedup"] = round(rec["gmres"]["solve_ms"] / rec["cg"]["solve_ms"], 3)
+    for k in ("cg", "bicgstab"):
+        if k in flags:
+            rec[k + "_speedup"] = round(rec["gmres"]["solve_ms"] / rec[k]["solve_ms"], 3)
+    if "cg" in flags and "bicgstab" in flags:
+        rec["bicgstab_over_cg_us_per_iter"] = round(rec["bicgstab"]["us_per_iter"] / rec["cg"]["us_per_iter"], 3)
     return rec
 
 
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--grid", type=int, default=None, help="grid side (default: bench.py's)")
-    p.add_argument("--solves", type=int, default=None, help="timed solves (default 3; 5 of each method with --cg)")
+    p.add_argument("--solves", type=int, default=None,
+                   help="timed solves (default 3; 5 of each method with --cg or --bicgstab)")
     p.add_argument("--cg", action="store_true", help="GMRES(restart) and CG (GG_SOLVE_CG) side by side")
+    p.add_argument("--bicgstab", action="store_true",
+                   help="GMRES(restart) and BiCGStab (GG_SOLVE_BICGSTAB) side by side, and CG when --upwind is 0")
+    p.add_argument("--upwind", type=float, default=0.0,
+                   help="with --bicgstab: west entries times 1 + U, east entries times 1 - U (nonsymmetric)")
     p.add_argument("--reps", type=int, default=50, help="applications per gg_time_precond call")
     p.add_argument("--drop-tol", type=float, default=0.1)
     p.add_argument("--only", default="ilu0,ainv,diag,none")
     p.add_argument("--out", default=None, help="also append the lines to this file")
     a = p.parse_args()
+    if a.cg and a.bicgstab:
+        p.error("--cg and --bicgstab exclude each other (--bicgstab --upwind 0 runs CG as well)")
+    if a.upwind != 0.0 and not a.bicgstab:
+        p.error("--upwind needs --bicgstab (GMRES alone and CG are measured on the bench's own system)")
     if a.solves is None:
-        a.solves = 5 if a.cg else 3
+        a.solves = 5 if (a.cg or a.bicgstab) else 3
     bench, d = bench_defaults()
     import ggmres
     from ggmres import matrices as M
 
     grid = a.grid or d.grid
-    A = M.laplacian_5pt(grid)              # bench.py main(): the C2 system
+    # bench.py main(): the C2 system (--upwind 0 passes nothing on: the same matrix)
+    A = M.laplacian_5pt(grid, upwind=a.upwind) if a.upwind != 0.0 else M.laplacian_5pt(grid)
     b = M.rhs_ones(A)
     n = A.shape[0]
     lines = []
@@ -110,7 +132,14 @@ def main():
         setters[kind]()
         setup = time.perf_counter() - t0
         if a.cg:
-            emit(side_by_side(s, ggmres, b, kind, n, grid, d, setup, max(1, a.solves)))
+            flags = {"gmres": 0, "cg": ggmres.SOLVE_CG}
+            emit(side_by_side(s, flags, b, kind, n, grid, d, setup, max(1, a.solves)))
+            continue
+        if a.bicgstab:
+            flags = {"gmres": 0, "bicgstab": ggmres.SOLVE_BICGSTAB}
+            if a.upwind == 0.0:
+                flags["cg"] = ggmres.SOLVE_CG
+            emit(side_by_side(s, flags, b, kind, n, grid, d, setup, max(1, a.solves), upwind=a.upwind))
             continue
         ms, g = [], None
         for _ in range(max(1, a.solves)):
