@@ -6,6 +6,8 @@ MODE
   ipc:<case>      one shard per process over GG_DD_IPC (device-initiated
                   exchanges through hipIpc-mapped areas); the handles are
                   all-gathered over torch.distributed "gloo" (CPU)
+  ipcm:<case>     the same communicator, a LONG_CASES system: restart lengths
+                  above 32 and above 64 (run_long)
   nccl_rccl       world size 1: torch.distributed "nccl" initialised first and
                   used, then the sharded solve over its own RCCL communicator
                   (GG_DD_RCCL, one rank) -- bench.py's library pairing at N > 1
@@ -30,11 +32,20 @@ CASES = {
     "5pt_200x160_P4": ("laplacian_5pt", (200, 160), "blocks"),
     "5pt_96x150_P3_bisect": ("laplacian_5pt", (96, 150), "bisect"),
 }
+# restart lengths above 32 (mode ipcm:<case>; apart from CASES: run() does not take them)
+LONG_CASES = {
+    "5pt_96x80_P2": ("laplacian_5pt", (96, 80), "blocks"),
+}
+# (key suffix, restart, max_iter, CGS2), all with tol 1e-300 and b = A 1: a
+# 40-column cycle -- with GG_DD_XK=1 CGS2 starts it on the in-kernel exchanges
+# and hands over to the all-gather launches at i = 32, on one sequence counter
+# -- and a cycle cut at 10 columns; 72 columns, the serial Update
+LONG_RUNS = (("m40", 40, 50, False), ("c40", 40, 50, True), ("m72", 72, 90, False))
 
 
 def system(case):
     from ggmres import host, matrices as M
-    fn, args, meth = CASES[case]
+    fn, args, meth = CASES[case] if case in CASES else LONG_CASES[case]
     A = getattr(M, fn)(*args)
     method = host.PART_BLOCKS if meth == "blocks" else host.PART_BISECT
     return A, method
@@ -62,6 +73,18 @@ def run(d, A, n, out):
     out.update(x3=np.where(own, g3["x"], np.nan), hist3=g3["hist"], iters3=g3["iters"], ret3=g3["ret"])
 
 
+def run_long(d, A, n, out):
+    import ggmres
+    from ggmres import matrices as M
+    x = np.random.default_rng(11).standard_normal(n)
+    own = ~np.isnan(d.spmv(x, np.full(n, np.nan)))          # the rows this process writes back
+    b = M.rhs_ones(A)
+    for key, m, max_iter, cgs2 in LONG_RUNS:
+        g = d.solve(b, restart=m, max_iter=max_iter, tol=1e-300, flags=ggmres.SOLVE_CGS2 if cgs2 else 0)
+        out.update({f"x_{key}": np.where(own, g["x"], np.nan), f"hist_{key}": g["hist"],
+                    f"iters_{key}": g["iters"], f"inner_{key}": g["inner"], f"ret_{key}": g["ret"]})
+
+
 def main():
     mode, outdir = sys.argv[1], sys.argv[2]
     rank = int(os.environ["RANK"])
@@ -70,8 +93,8 @@ def main():
     import torch.distributed as dist
     from ggmres.dd import DD, unique_id
     out = {}
-    if mode.startswith("ipc:"):
-        case = mode[4:]
+    if mode.startswith(("ipc:", "ipcm:")):
+        case = mode.split(":", 1)[1]
         dist.init_process_group("gloo", rank=rank, world_size=world)
         d = DD(world, device=0, rank=rank, comm="ipc")
 
@@ -129,7 +152,10 @@ def main():
     d.set_system(A, method)
     out["info"] = np.array(list(d.info().values()))
     out["q"] = d.perm()[1]
-    run(d, A, n, out)
+    if mode.startswith("ipcm:"):
+        run_long(d, A, n, out)
+    else:
+        run(d, A, n, out)
     d.close()
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), **{k: np.asarray(v) for k, v in out.items()})
     dist.destroy_process_group()

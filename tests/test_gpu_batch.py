@@ -76,6 +76,46 @@ def test_solve_batch_bitexact_vs_single(grid, m, max_iter, tol, division):
     s.close()
 
 
+def test_solve_batch_long_restart_bitexact_vs_single():
+    """Restart lengths at the batch's other Update forms (launch_update_b):
+    m = 1 (k = 0 every cycle), m = 64 (lane 63 of the one-wave k_update_y) and
+    m = 80 (k_update_y_serial, with the scenario stride), fixed-length runs of
+    three scenarios -- a pair and a single for the two-scenario launches, one
+    warm start -- each bit-identical to its own single solve (which
+    test_gpu_parity.py's test_edge_cases pins to the oracle at these (m,
+    max_iter) on this matrix); then restart 30 on the same solver: the batch
+    workspace rebuilt for a shorter basis."""
+    A = M.laplacian_5pt(100, 100)
+    n = A.shape[0]
+    S = 3
+    rng = np.random.default_rng(3)
+    B = np.array([M.rhs_uniform(n), rng.standard_normal(n), 1e3 * rng.uniform(-1, 1, n)])
+    X0 = np.zeros((S, n))
+    X0[1] = np.random.default_rng(9).standard_normal(n) * 1e-2       # a warm start
+    runs = [dict(restart=1, max_iter=7, tol=1e-300), dict(restart=64, max_iter=100, tol=1e-300),
+            dict(restart=80, max_iter=170, tol=1e-300), dict(restart=30, max_iter=3000, tol=1e-10)]
+    s = ggmres.Solver(0)
+    s.set_matrix(A)
+    s.set_precond_ilu0()
+    assert s.uses_wavefront and s.batch_engine
+    refs = [_single(s, B, X0, **kw) for kw in runs]
+    for kw, ref in zip(runs, refs):                  # the batches back to back: 1, 64, 80, then 30 columns
+        g = s.solve_batch(B, X0, **kw)
+        for q in range(S):
+            r = ref[q]
+            assert np.all(np.isfinite(r["hist"])), (kw, q)
+            if kw["tol"] == 1e-300:
+                assert (r["ret"], r["iters"]) == (1, kw["max_iter"]), (kw, q)
+            else:
+                assert r["ret"] == 0, (kw, q)
+            assert (g["status"][q], g["iters"][q], g["inner"][q], g["restarts"][q]) == \
+                   (r["ret"], r["iters"], r["inner"], r["restarts"]), (kw, q)
+            assert g["relres"][q] == r["relres"], (kw, q)
+            assert np.array_equal(g["hist"][q], r["hist"]), (kw, q)
+            assert np.array_equal(g["x"][q], r["x"]), (kw, q)
+    s.close()
+
+
 def test_solve_batch_vs_order_matched_oracle():
     """one batch, every scenario against the order-matched oracle (bit-identical)
     and the serial-order oracle (1e-10), GMRES(30) + ILU(0), exact division"""

@@ -13,6 +13,7 @@ The RCCL communicator is exercised with one rank (the GPU box has one GPU).
 import numpy as np
 import pytest
 
+import ggmres
 import oracle as O
 from conftest import fixture_path
 from ggmres import host, matrices as M
@@ -240,6 +241,147 @@ def test_dd_division_rcp_tolerance(name, mode):
             assert abs(g["iters"] - ref["iters"]) <= max(2, ref["iters"] // 50), (g["iters"], ref["iters"])
     finally:
         d.set_division(ggmres.DIV_EXACT)
+
+
+# ---- restart lengths above 32 and above 64 --------------------------------------
+# The orthogonalization and the Update change form with the restart length:
+# CGS2's fused k_cgs_update_dot and one-chunk k_cgs_update hold for i + 1 <= 32
+# dots (beyond: k_multidot rows past the fourth, k_cgs_reduce with more than 32
+# blocks, two chunks in k_cgs_update), the one-wave k_update_y for m <= 64
+# (beyond: k_update_y_serial).  Small systems of their own (not in CASES: the
+# parametrized tests above do not grow), b = A 1, both orthogonalizations.
+LONG_CASES = {
+    # name: (matrix, parts, method)
+    "5pt_96x80_P2": (lambda: M.laplacian_5pt(96, 80), 2, host.PART_BLOCKS),
+    "5pt_96x80_P4_color": (lambda: M.laplacian_5pt(96, 80), 4, host.PART_BLOCKS | host.PART_COLOR_SEP),
+    "7pt_16x16x24_P4_upwind": (lambda: M.grid_7pt(16, 16, 24, upwind=0.1), 4, host.PART_BLOCKS),
+}
+# fixed-length runs (tol 1e-300), (restart, max_iter): a 40-column cycle (dots
+# 33..40) and a cycle cut at 10 columns; the one-wave Update at k = 63; the
+# serial Update after a full 72-column cycle and after a cut one; an Update
+# with k = 0 every cycle.  The 3D case reaches 1e-12 within 72 columns (a
+# stagnated cycle would compare rounding noise), so it takes no 64 / 72 run.
+LONG_FIXED = {
+    "5pt_96x80_P2": [(40, 50), (64, 64), (72, 90), (1, 5)],
+    "5pt_96x80_P4_color": [(40, 50), (64, 64), (72, 90), (1, 5)],
+    "7pt_16x16x24_P4_upwind": [(40, 50), (1, 5)],
+}
+ORTH = {"mgs": 0, "cgs2": ggmres.SOLVE_CGS2}
+
+_long_cache = {}
+_long_refs = {}
+
+
+def setup_long(name):
+    """setup()'s sibling for LONG_CASES: (A, d, q, B, L, U, b, dot segments, G)"""
+    if name not in _long_cache:
+        make, P, method = LONG_CASES[name]
+        A = make()
+        d = DD(P, device=0)
+        d.set_system(A, method)
+        pinv, q = d.perm()
+        B = host.permute(A, pinv, q)
+        L, U = O.ilu0(B)
+        segs, G = zip(*[d.dot_layout(p) for p in range(P)])
+        _long_cache[name] = (A, d, q, B, L, U, M.rhs_ones(A), list(segs), G[0])
+    return _long_cache[name]
+
+
+def long_ref(name, orth, m, max_iter, tol, matched=True):
+    """the oracle on B = P A P^T, once per run: in the sharded reduction order
+    with orth's orthogonalization (matched), or the serial-order MGS reference"""
+    key = (name, orth if matched else None, m, max_iter, tol)
+    if key not in _long_refs:
+        A, d, q, B, L, U, b, segs, G = setup_long(name)
+        if matched:
+            O.set_dot_order_shards(segs, G)
+            O.set_orth(orth == "cgs2")
+        try:
+            _long_refs[key] = O.gmres_left(B, L, U, b[q], m=m, max_iter=max_iter, tol=tol)
+        finally:
+            O.set_dot_order(None)
+            O.set_orth()
+    return _long_refs[key]
+
+
+def check_fixed_inputs(ref, m, max_iter):
+    """conditions on a fixed-length reference run, before the device is compared:
+    it used every iteration, its history is finite and ends far above rounding
+    level (a stagnated cycle's columns are noise) with every cycle at full length"""
+    assert ref["ret"] == 1 and ref["iters"] == max_iter
+    assert len(ref["hist"]) == 1 + max_iter + -(-max_iter // m)
+    assert np.all(np.isfinite(ref["hist"]))
+    assert ref["hist"][-1] > 1e-11, ref["hist"][-1]
+
+
+def check_bits(g, ref, q):
+    assert g["ret"] == ref["ret"] and g["iters"] == ref["iters"], (g["ret"], g["iters"], ref["ret"], ref["iters"])
+    assert g["hist"].shape == ref["hist"].shape
+    assert np.array_equal(g["hist"], ref["hist"])
+    assert np.array_equal(g["x"][q], ref["x"])
+
+
+@pytest.mark.parametrize("orth", sorted(ORTH))
+@pytest.mark.parametrize("name,m,max_iter", [(n, m, mi) for n in sorted(LONG_FIXED) for m, mi in LONG_FIXED[n]])
+def test_dd_long_restart_fixed_length_bitexact(name, m, max_iter, orth):
+    """restart 40 / 64 / 72 / 1 for a fixed number of iterations: return code,
+    iteration count, the whole history and x bit-identical to the oracle in
+    the sharded reduction order"""
+    A, d, q, B, L, U, b, segs, G = setup_long(name)
+    ref = long_ref(name, orth, m, max_iter, 1e-300)
+    check_fixed_inputs(ref, m, max_iter)
+    g = d.solve(b, restart=m, max_iter=max_iter, tol=1e-300, flags=ORTH[orth])
+    assert g["ret"] == 1 and g["iters"] == max_iter
+    check_bits(g, ref, q)
+
+
+@pytest.mark.parametrize("orth", sorted(ORTH))
+@pytest.mark.parametrize("name", sorted(LONG_CASES))
+def test_dd_long_restart_converges_bitexact(name, orth):
+    """restart 40 to convergence: every cycle passes 33..40 dots; bit-identical
+    to the order-matched oracle, MGS within 1e-10 of the serial-order oracle
+    (check_serial), CGS2 with a true preconditioned residual below 1e-9"""
+    A, d, q, B, L, U, b, segs, G = setup_long(name)
+    ref_t = long_ref(name, orth, 40, 1500, 1e-10)
+    assert ref_t["ret"] == 0 and ref_t["iters"] > 40          # a full 40-column first cycle
+    assert np.all(np.isfinite(ref_t["hist"]))
+    g = d.solve(b, restart=40, max_iter=1500, tol=1e-10, flags=ORTH[orth])
+    assert g["ret"] == ref_t["ret"] == 0
+    assert g["iters"] == ref_t["iters"]
+    check_bits(g, ref_t, q)
+    if orth == "mgs":
+        check_serial(g, long_ref(name, None, 40, 1500, 1e-10, matched=False), x_g=g["x"][q], tol=1e-10)
+    else:
+        normb = np.linalg.norm(O.lusolve(L, U, b[q]))
+        true = np.linalg.norm(O.lusolve(L, U, b[q] - O.spmv(B, g["x"][q]))) / normb
+        assert true < 1e-9, true
+
+
+@pytest.mark.parametrize("name", sorted(LONG_CASES))
+def test_dd_workspace_resized_between_restarts(name):
+    """the workspace follows the restart length (ensure_workspace, m_alloc: the
+    basis, H, and the CGS2 partials' two halves at P (m + 1) G): after this
+    case's 72- (40-), 1- and 40-column solves on one DD, the first restart-40
+    CGS2 solve and restart-30 solves have the bits of the same solves on a
+    freshly created DD (and of the oracle)"""
+    A, d, q, B, L, U, b, segs, G = setup_long(name)
+    _, P, method = LONG_CASES[name]
+    for m in [m for m, _ in LONG_FIXED[name]] + [40]:       # 40, (64, 72,) 1, 40 columns
+        d.solve(b, restart=m, max_iter=m + 3, tol=1e-300, flags=ORTH["cgs2"])
+    fresh = DD(P, device=0)
+    fresh.set_system(A, method)
+    try:
+        for m, max_iter, orth in ((40, 50, "cgs2"), (30, 45, "cgs2"), (30, 45, "mgs")):
+            ref = long_ref(name, orth, m, max_iter, 1e-300)
+            check_fixed_inputs(ref, m, max_iter)
+            g = d.solve(b, restart=m, max_iter=max_iter, tol=1e-300, flags=ORTH[orth])
+            f = fresh.solve(b, restart=m, max_iter=max_iter, tol=1e-300, flags=ORTH[orth])
+            assert (g["ret"], g["iters"], g["inner"], g["restarts"]) == \
+                   (f["ret"], f["iters"], f["inner"], f["restarts"]), (m, orth)
+            assert np.array_equal(g["hist"], f["hist"]) and np.array_equal(g["x"], f["x"]), (m, orth)
+            check_bits(g, ref, q)
+    finally:
+        fresh.close()
 
 
 def test_single_solver_refuses_cgs2():

@@ -147,6 +147,69 @@ def test_dd_ipc_ranks_match_local_and_oracle(case, xk, tmp_path):
     assert np.array_equal(merge(rs, "x")[q], ref["x"])
 
 
+@pytest.mark.parametrize("xk", [0, 1])
+def test_dd_ipc_ranks_long_restart(xk, tmp_path):
+    """Restart lengths above 32 and above 64 over the ranks (worker mode ipcm,
+    W.LONG_RUNS): GMRES(40) with MGS and with CGS2 -- with xk = 1 a CGS2 cycle
+    starts on the in-kernel exchanges and, from i = 32 (33 dots, beyond
+    kCgsXMax), goes on with the all-gather launches on the same sequence
+    counter and exchange area; MGS keeps its in-kernel exchanges for every
+    column -- and GMRES(72) with MGS (the serial Update).  Every rank agrees,
+    and the results are bit-identical to the one-process GG_DD_LOCAL solves
+    and to the oracle in the sharded reduction order."""
+    import ggmres
+    case = "5pt_96x80_P2"
+    P = 2
+    rs = run_ranks(f"ipcm:{case}", P, tmp_path, xk=xk)
+    A, method = W.system(case)
+    keys = [k for k, _, _, _ in W.LONG_RUNS]
+    for r in rs[1:]:
+        assert np.array_equal(r["q"], rs[0]["q"])
+        for k in keys:
+            assert np.array_equal(r[f"hist_{k}"], rs[0][f"hist_{k}"]), k
+            for f in ("iters", "inner", "ret"):
+                assert int(r[f"{f}_{k}"]) == int(rs[0][f"{f}_{k}"]), (f, k)
+    inf = rs[0]["info"]
+    assert inf[1] == P and inf[8] == 1            # nparts, one shard in this process
+    loc = DD(P, device=0)
+    loc.set_system(A, method)
+    pinv, q = loc.perm()
+    assert np.array_equal(q, rs[0]["q"])
+    segs, G = zip(*[loc.dot_layout(p) for p in range(P)])
+    # the in-kernel exchanges ran (or not), as test_dd_ipc_ranks_match_local_and_oracle expects
+    assert int(inf[10]) == int(xk and P * G[0] <= 256), inf
+    B = host.permute(A, pinv, q)
+    L, U = O.ilu0(B)
+    b = M.rhs_ones(A)
+    try:
+        for key, m, max_iter, cgs2 in W.LONG_RUNS:
+            # the oracle on B in the sharded reduction order; its run is of full
+            # length and ends far above rounding level
+            O.set_dot_order_shards(list(segs), G[0])
+            O.set_orth(cgs2)
+            try:
+                ref = O.gmres_left(B, L, U, b[q], m=m, max_iter=max_iter, tol=1e-300)
+            finally:
+                O.set_dot_order(None)
+                O.set_orth()
+            assert ref["ret"] == 1 and ref["iters"] == max_iter
+            assert np.all(np.isfinite(ref["hist"])) and ref["hist"][-1] > 1e-11
+            assert len(ref["hist"]) == 1 + max_iter + -(-max_iter // m)
+            # the same decomposition in one process (GG_DD_LOCAL)
+            g = loc.solve(b, restart=m, max_iter=max_iter, tol=1e-300, flags=ggmres.SOLVE_CGS2 if cgs2 else 0)
+            r0 = rs[0]
+            assert int(r0[f"ret_{key}"]) == g["ret"] == 1, key
+            assert int(r0[f"iters_{key}"]) == g["iters"] == max_iter, key
+            assert int(r0[f"inner_{key}"]) == g["inner"], key
+            assert np.array_equal(r0[f"hist_{key}"], g["hist"]), key
+            x = merge(rs, f"x_{key}")
+            assert np.array_equal(x, g["x"]), key
+            assert np.array_equal(r0[f"hist_{key}"], ref["hist"]), key
+            assert np.array_equal(x[q], ref["x"]), key
+    finally:
+        loc.close()
+
+
 @pytest.mark.parametrize("form", ["second_stream", "separate_launches"])
 def test_dd_ipc_ranks_halo_forms(form, tmp_path):
     """The SpMV's interface exchange in the other two forms than the default

@@ -588,6 +588,37 @@ def test_edge_cases(solver):
         check_exact(g, ot)
 
 
+@pytest.mark.parametrize("path", ["per_step", "wide"])
+def test_edge_restarts_other_orthogonalizations(path, monkeypatch):
+    """test_edge_cases' restart lengths -- m = 1, m = 64 (lane 63 of the
+    one-wave Update) and m = 80 (the serial Update) -- on the two
+    orthogonalizations it does not take: the per-step kernels
+    (GG_NO_PERSIST=1) against both oracles, k_arnoldi_wide (GG_WIDE_FORCE=1)
+    against the oracle in its 512-block order.  A solver of its own: both
+    settings are read when the space and the workspace are built."""
+    monkeypatch.setenv("GG_NO_PERSIST" if path == "per_step" else "GG_WIDE_FORCE", "1")
+    A = M.laplacian_5pt(100)
+    n = A.shape[0]
+    L, U = O.ilu0(A)
+    b = M.rhs_uniform(n)
+    lay, G = device_layout(n, nx=100)
+    s = ggmres.Solver(0)
+    try:
+        s.set_matrix(A)
+        s.set_precond_ilu0()
+        assert s.uses_wavefront
+        for m, mi in ((1, 17), (64, 100), (80, 170)):
+            run = lambda: O.gmres_left(A, L, U, b, m=m, max_iter=mi, tol=1e-300)
+            o, ot = oracle_both(run, n, layout=(lay, G if path == "per_step" else 512))
+            assert o["ret"] == 1 and o["iters"] == mi and np.all(np.isfinite(ot["hist"]))
+            g = s.solve(b, restart=m, max_iter=mi, tol=1e-300)
+            if path == "per_step":
+                check_gmres(g, o)
+            check_exact(g, ot)
+    finally:
+        s.close()
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, 127, 513])
 def test_small_and_ragged_sizes(solver, n):
     """Sizes around the 64-lane, 256-thread and 512-slot paddings: a seeded
