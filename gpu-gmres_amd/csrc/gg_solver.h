@@ -2,6 +2,7 @@
 // and the many-RHS batch driver (batch.hip).
 #pragma once
 
+#include <algorithm>
 #include <vector>
 
 #include "kernels.h"
@@ -18,19 +19,42 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
                 const gg_options *opt, gg_result *res);
 bool batch_engine_on(gg_solver *s);
 long long batch_history(gg_solver *s, int q, double *out, long long cap);
-// cg.hip: the GG_SOLVE_CG engine behind solve_device (arguments checked by the
-// caller, s->shared set) and the release of its pinned slots (gg_destroy)
+// cg.hip, bicgstab.hip: the GG_SOLVE_CG and GG_SOLVE_BICGSTAB engines behind
+// solve_device (arguments checked by the caller, s->shared set); both are
+// short_recurrence.h's driver over their own launches
 int solve_cg(gg_solver *s, const double *d_b, double *d_x, const gg_options *opt, gg_result *res);
-void cg_release(gg_solver *s);
-// bicgstab.hip: the GG_SOLVE_BICGSTAB engine, likewise
 int solve_bicgstab(gg_solver *s, const double *d_b, double *d_x, const gg_options *opt, gg_result *res);
-void bicgstab_release(gg_solver *s);
-// solver.hip, shared with cg.hip and bicgstab.hip.  Fallback: a wavefront solve asked for a
-// repeat on its safe path (the error word's bits 1 and 3); solve_device applies
-// it and starts the solve over
+// solver.hip, shared with short_recurrence.h.  Fallback: a wavefront solve asked
+// for a repeat on its safe path (the error word's bits 1 and 3); solve_device
+// applies it and starts the solve over
 struct Fallback {
     int bits;
 };
+// The device error word (solver.hip check_err) into the throw or the raise, in
+// this order: bit 3 -> Fallback, bit 0 -> GG_ETIMEOUT, bit 1 -> Fallback.
+// Returns when none of kErrSolve is set.
+constexpr int kErrSolve = 8 | 1 | 2;
+void raise_err(int err);
+// The read-back pipe (solver.hip): a solve enqueues work one unit (a restart
+// cycle, a chunk of iterations) ahead of the state the host has read.  Each
+// unit ends in a post: the control block and the error word copied into one of
+// two pinned slots, then an event.  A solver runs one solve at a time, so one
+// pipe serves GMRES, CG and BiCGStab.
+struct ReadPipe {
+    void *state[2] = {nullptr, nullptr};    // kPipeSlotBytes each
+    int *err[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<size_t> mark_ends;          // marks.size() after each posted unit not yet collected
+};
+constexpr size_t kPipeSlotBytes = std::max({sizeof(DevState), sizeof(CgState), sizeof(BiState)});
+void pipe_begin(gg_solver *s);              // slots and events allocated once; nothing posted
+// the state (bytes at dev_state) and the error word into the slot, then its
+// event; close_marks: the profile marks enqueued so far end a unit here
+void pipe_post(gg_solver *s, int slot, const void *dev_state, size_t bytes, bool close_marks = true);
+int pipe_wait(gg_solver *s, int slot);      // the slot's error word; its state: pipe_state (below)
+void pipe_collect(gg_solver *s, int executed);      // the oldest posted unit's marks
+void pipe_drain(gg_solver *s);              // waits for the unit behind the last (gated off), drops its marks
+void pipe_release(gg_solver *s);            // gg_destroy
 // the Ppad-long work vectors, partials, control block, error word; bicgstab: also the
 // three vectors that solve alone keeps (bi_rt, bi_t, bi_q)
 void ensure_vectors(gg_solver *s, bool bicgstab = false);
@@ -108,35 +132,20 @@ struct gg_solver {
     bool wide = false;                  // k_arnoldi_wide (vectors beyond persist's registers)
     bool shared = false;                // GG_SOLVE_SHARED_DEVICE for the solve in progress
     int div_mode = GG_DIV_EXACT;        // gg_set_division: the wavefront solves' division
-    // pinned host copies of the control block and the error word (one
-    // round trip per restart cycle reads both)
-    DevState *h_state = nullptr;
-    int *h_err = nullptr;
-    // the pipelined cycle loop: two pinned slots, each the state after one cycle
-    DevState *p_state[2] = {nullptr, nullptr};
-    int *p_err[2] = {nullptr, nullptr};
-    hipEvent_t p_ev[2] = {nullptr, nullptr};
-    std::vector<size_t> mark_ends;      // marks.size() after each enqueued cycle (pipelined)
+    gg::ReadPipe pipe;                  // pinned read-backs of the control block and the error word
     int resid_fallbacks = 0;            // cycles rerun after a persistent grid was not co-resident
     int iter_hint = 0;                  // transient loop: the previous step's inner iterations (0: none)
-    // GG_SOLVE_CG (cg.hip): control block, the dots' block partials (p.q | r.z, z.z),
-    // two pinned slots for the chunk loop's read-backs
+    // GG_SOLVE_CG and GG_SOLVE_BICGSTAB (short_recurrence.h): the control blocks and the
+    // dots' block partials (1024 each; cg.hip: p.q | r.z, z.z; bicgstab.hip: rt.v | t.s, t.t |
+    // r.r, rt.r)
     DBuf<gg::CgState> cgs;
-    DBuf<double> cg_part;
-    gg::CgState *cg_state[2] = {nullptr, nullptr};
-    int *cg_err[2] = {nullptr, nullptr};
-    hipEvent_t cg_ev[2] = {nullptr, nullptr};
-    bool last_cg = false;               // the last solve ran CG or BiCGStab (gg_mgs_kernel: no orthogonalization)
-    // GG_SOLVE_BICGSTAB (bicgstab.hip): control block, the dots' block partials
-    // (rt.v | t.s, t.t | r.r, rt.r), the vectors beyond the GMRES work space
-    // (the shadow residual, t, the SpMV output M is applied to), pinned slots
     DBuf<gg::BiState> bis;
-    DBuf<double> bi_part;
+    DBuf<double> sr_part;
+    bool last_cg = false;               // the last solve ran CG or BiCGStab (gg_mgs_kernel: no orthogonalization)
+    // BiCGStab's vectors beyond the GMRES work space (the shadow residual, t, the
+    // SpMV output M is applied to)
     DBuf<double> bi_rt, bi_t, bi_q;
     bool bi_vec_ok = false;
-    gg::BiState *bi_state[2] = {nullptr, nullptr};
-    int *bi_err[2] = {nullptr, nullptr};
-    hipEvent_t bi_ev[2] = {nullptr, nullptr};
     // transient tap-node statistics (gg_transient_set_taps / _get_taps)
     std::vector<int> taps;
     std::vector<double> tap_max, tap_min, tap_avg;
@@ -168,3 +177,12 @@ struct gg_solver {
     // batched solves of the same shape
     gg::BatchWs *batch = nullptr;
 };
+
+namespace gg {
+// the state a post copied into the slot (after pipe_wait)
+template <class State>
+const State &pipe_state(const gg_solver *s, int slot)
+{
+    return *static_cast<const State *>(s->pipe.state[slot]);
+}
+}  // namespace gg

@@ -331,26 +331,29 @@ struct CgState {
     double normb, resid, tol;
     double alpha;       // the last step length (diagnostics)
     double rz[2];       // r . z entering iteration it at rz[it & 1]
-    int done;           // CG_* bits
+    int done;           // SR_* bits
     int it;             // iterations performed
     int max_iter;
     int pad;
 };
-constexpr int CG_CONV = 1, CG_BREAKDOWN = 2, CG_INIT = 4;
+// the done bits of the short-recurrence methods' control blocks (CgState, BiState;
+// short_recurrence.h): converged, broke down, converged at the start
+constexpr int SR_CONV = 1, SR_BREAKDOWN = 2, SR_INIT = 4;
 // With G = the reduction grid, part arrays of 2 G doubles, it = the iteration's
-// 0-based index:
-//   normb = sqrt(sum of part) (0 -> 1)
-void launch_cg_normb(const double *part, int G, CgState *cs, hipStream_t st);
+// 0-based index.  launch_normb, launch_cg_pq and launch_cg_rz are shared with
+// BiCGStab (plain reductions, no control block):
+//   *normb = sqrt(sum of part) (0 -> 1); normb = &state->normb of either control block
+void launch_normb(const double *part, int G, double *normb, hipStream_t st);
 //   part = block partials of p . q
 void launch_cg_pq(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, hipStream_t st);
-//   pq = sum of part; not pq > 0: CG_BREAKDOWN; alpha = rz / pq; x = alpha p + x; r = (-alpha) q + r
+//   pq = sum of part; not pq > 0: SR_BREAKDOWN; alpha = rz / pq; x = alpha p + x; r = (-alpha) q + r
 void launch_cg_xr(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
                   const double *q, long long Ppad, hipStream_t st);
 //   part = block partials of r . z, then of z . z
 void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, hipStream_t st);
-//   rzn, zz = sums of part; resid = hist[it + 1] = sqrt(zz) / normb; resid < tol: CG_CONV; else not
-//   rzn > 0: CG_BREAKDOWN; else p = (rzn / rz) p + z.  start (the initial residual, nothing
-//   counted): hist[0], resid <= tol: CG_INIT, p = z
+//   rzn, zz = sums of part; resid = hist[it + 1] = sqrt(zz) / normb; resid < tol: SR_CONV; else not
+//   rzn > 0: SR_BREAKDOWN; else p = (rzn / rz) p + z.  start (the initial residual, nothing
+//   counted): hist[0], resid <= tol: SR_INIT, p = z
 void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
                  double *hist, long long Ppad, hipStream_t st);
 
@@ -362,29 +365,26 @@ struct BiState {
     double normb, resid, tol;
     double alpha, omega;
     double rho[2];      // rt . r entering iteration it at rho[it & 1]
-    double bad;         // BI_BREAKDOWN: the scalar that was zero or not finite
-    int done;           // BI_* bits
+    double bad;         // SR_BREAKDOWN: the scalar that was zero or not finite
+    int done;           // SR_* bits
     int it;             // iterations performed
     int max_iter;
-    int why;            // BI_BREAKDOWN: which scalar (BI_WHY_*)
+    int why;            // SR_BREAKDOWN: which scalar (BI_WHY_*)
 };
-constexpr int BI_CONV = 1, BI_BREAKDOWN = 2, BI_INIT = 4;
 constexpr int BI_WHY_RHO = 1, BI_WHY_RTV = 2, BI_WHY_OMEGA = 3;
-// The two plain dot launches of an iteration are CG's: launch_cg_pq (rt . v)
-// and launch_cg_rz (t . s, then t . t).  it = the iteration's 0-based index.
-//   normb = sqrt(sum of part) (0 -> 1)
-void launch_bi_normb(const double *part, int G, BiState *bs, hipStream_t st);
-//   rtv = sum of part; zero or not finite: BI_BREAKDOWN; alpha = rho / rtv; r = s = (-alpha) v + r
+// normb and the two plain dot launches of an iteration are CG's: launch_normb,
+// launch_cg_pq (rt . v) and launch_cg_rz (t . s, then t . t).  it = the iteration's 0-based index.
+//   rtv = sum of part; zero or not finite: SR_BREAKDOWN; alpha = rho / rtv; r = s = (-alpha) v + r
 void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double *r, const double *v,
                  long long Ppad, hipStream_t st);
 //   ts, tt = sums of part_in; omega = tt > 0 ? ts / tt : 0; x = omega s + (alpha p + x);
 //   r = (-omega) t + s in place of s; part_out = block partials of r . r, then of rt . r
 void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, const double *p, double *s,
                   const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st);
-//   rr, rhon = sums of part; resid = hist[it + 1] = sqrt(rr) / normb; resid < tol: BI_CONV; else omega or
-//   rhon zero or not finite: BI_BREAKDOWN; else p = ((rhon / rho) (alpha / omega)) ((-omega) v + p) + r.
+//   rr, rhon = sums of part; resid = hist[it + 1] = sqrt(rr) / normb; resid < tol: SR_CONV; else omega or
+//   rhon zero or not finite: SR_BREAKDOWN; else p = ((rhon / rho) (alpha / omega)) ((-omega) v + p) + r.
 //   start (the initial residual, nothing counted; part = partials of r . r alone): hist[0], resid <= tol:
-//   BI_INIT, rho = rr zero or not finite: BI_BREAKDOWN, else rt = p = r
+//   SR_INIT, rho = rr zero or not finite: SR_BREAKDOWN, else rt = p = r
 void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
                  const double *r, double *rt, double *hist, long long Ppad, hipStream_t st);
 

@@ -5131,12 +5131,13 @@ __global__ void k_end_cycle(const double *part, int G, DevState *ds, double *his
 // block that sees them early returns where it would have returned anyway
 // (every block forms the same scalars).  rz alternates between two words: the
 // launch that forms iteration it's beta from rz[it & 1] stores the next one.
-__global__ void k_cg_normb(const double *part, int G, CgState *cs)
+// (k_normb, k_cg_pq and k_cg_rz touch no control block: BiCGStab launches them too.)
+__global__ void k_normb(const double *part, int G, double *normb)
 {
     const double s = sum_partials(part, G);
     if (threadIdx.x == 0) {
         const double nb = sqrt(s);
-        cs->normb = (nb == 0.0) ? 1.0 : nb;
+        *normb = (nb == 0.0) ? 1.0 : nb;
     }
 }
 
@@ -5194,7 +5195,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_xr(Gate g, int it, CgState *cs, c
     const double rz = cs->rz[it & 1];
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
     if (!(pq > 0.0)) {
-        if (first) cs->done = CG_BREAKDOWN;
+        if (first) cs->done = SR_BREAKDOWN;
         return;
     }
     const double alpha = rz / pq;
@@ -5281,8 +5282,8 @@ __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, co
         hist[done_it] = res;
         cs->it = done_it;
         cs->rz[done_it & 1] = rzn;
-        if (conv) cs->done = START ? CG_INIT : CG_CONV;
-        else if (brk) cs->done = CG_BREAKDOWN;
+        if (conv) cs->done = START ? SR_INIT : SR_CONV;
+        else if (brk) cs->done = SR_BREAKDOWN;
     }
     if (conv || brk) return;
     const double beta = START ? 0.0 : rzn / rz;
@@ -5314,15 +5315,6 @@ __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, co
 // read by later ones only; rho alternates between two words like CG's rz.
 __device__ __forceinline__ bool bi_bad(double v) { return !isfinite(v) || v == 0.0; }
 
-__global__ void k_bi_normb(const double *part, int G, BiState *bs)
-{
-    const double s = sum_partials(part, G);
-    if (threadIdx.x == 0) {
-        const double nb = sqrt(s);
-        bs->normb = (nb == 0.0) ? 1.0 : nb;
-    }
-}
-
 // rtv from the partials (breakdown when zero or not finite: nothing moves);
 // alpha = rho / rtv;  s = (-alpha) v + r in place of r
 __global__ __launch_bounds__(kBlock) void k_bi_s(Gate g, int it, BiState *bs, const double *part, int G,
@@ -5351,7 +5343,7 @@ __global__ __launch_bounds__(kBlock) void k_bi_s(Gate g, int it, BiState *bs, co
         if (first) {
             bs->bad = rtv;
             bs->why = BI_WHY_RTV;
-            bs->done = BI_BREAKDOWN;
+            bs->done = SR_BREAKDOWN;
         }
         return;
     }
@@ -5475,12 +5467,12 @@ __global__ __launch_bounds__(kBlock) void k_bi_p(Gate g, int it, BiState *bs, co
         hist[done_it] = res;
         bs->it = done_it;
         bs->rho[done_it & 1] = rhon;
-        if (conv) bs->done = START ? BI_INIT : BI_CONV;
+        if (conv) bs->done = START ? SR_INIT : SR_CONV;
         else if (brk) {
             const bool om = bi_bad(omega);
             bs->bad = om ? omega : rhon;
             bs->why = om ? BI_WHY_OMEGA : BI_WHY_RHO;
-            bs->done = BI_BREAKDOWN;
+            bs->done = SR_BREAKDOWN;
         }
     }
     if (conv || brk) return;
@@ -6657,9 +6649,9 @@ void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, i
 }
 
 // ---- CG (cg.hip) ----------------------------------------------------------------
-void launch_cg_normb(const double *part, int G, CgState *cs, hipStream_t st)
+void launch_normb(const double *part, int G, double *normb, hipStream_t st)
 {
-    k_cg_normb<<<1, kBlock, 0, st>>>(part, G, cs);
+    k_normb<<<1, kBlock, 0, st>>>(part, G, normb);
 }
 void launch_cg_pq(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, hipStream_t st)
 {
@@ -6682,10 +6674,6 @@ void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, in
 }
 
 // ---- BiCGStab (bicgstab.hip) ------------------------------------------------------
-void launch_bi_normb(const double *part, int G, BiState *bs, hipStream_t st)
-{
-    k_bi_normb<<<1, kBlock, 0, st>>>(part, G, bs);
-}
 void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double *r, const double *v,
                  long long Ppad, hipStream_t st)
 {

@@ -1316,34 +1316,84 @@ void gg::reset_wave(DevTri *T, hipStream_t st)
 // 3 = a statically dealt tile grid was not co-resident (repeat with the tile
 // queue, k_trsv_tile3d).  Bits 1 and 3 throw Fallback: the caller applies it
 // (apply_fallback) and repeats the solve / apply.  (struct Fallback: gg_solver.h)
+void gg::raise_err(int err)
+{
+    if (err & 8) throw Fallback{err};              // (the residency timeout also left garbage)
+    GG_REQUIRE((err & 1) == 0, GG_ETIMEOUT, "wavefront triangular solve: boundary wait timed out");
+    if (err & 2) throw Fallback{err};
+}
 void gg::check_err(gg_solver *s)
 {
     // on the solver's stream: a plain hipMemcpy would not wait for its kernels
     int err = 0;
     GG_HIP(hipMemcpyAsync(&err, s->err.p, sizeof(int), hipMemcpyDeviceToHost, s->st));
     GG_HIP(hipStreamSynchronize(s->st));
-    if (err & 8) throw Fallback{err};              // (the residency timeout also left garbage)
-    GG_REQUIRE((err & 1) == 0, GG_ETIMEOUT, "wavefront triangular solve: boundary wait timed out");
-    if (err & 2) throw Fallback{err};
+    raise_err(err);
+}
+
+// ---- the read-back pipe (gg_solver.h ReadPipe) --------------------------------
+void gg::pipe_begin(gg_solver *s)
+{
+    ReadPipe &p = s->pipe;
+    for (int k = 0; k < 2; k++)
+        if (!p.ev[k]) {
+            GG_HIP(hipHostMalloc(&p.state[k], kPipeSlotBytes, hipHostMallocDefault));
+            GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&p.err[k]), sizeof(int), hipHostMallocDefault));
+            GG_HIP(hipEventCreateWithFlags(&p.ev[k], hipEventDisableTiming));
+        }
+    p.mark_ends.clear();
+}
+void gg::pipe_post(gg_solver *s, int slot, const void *dev_state, size_t bytes, bool close_marks)
+{
+    ReadPipe &p = s->pipe;
+    if (close_marks) p.mark_ends.push_back(s->marks.size());
+    GG_HIP(hipMemcpyAsync(p.state[slot], dev_state, bytes, hipMemcpyDeviceToHost, s->st));
+    GG_HIP(hipMemcpyAsync(p.err[slot], s->err.p, sizeof(int), hipMemcpyDeviceToHost, s->st));
+    GG_HIP(hipEventRecord(p.ev[slot], s->st));
+}
+int gg::pipe_wait(gg_solver *s, int slot)
+{
+    GG_HIP(hipEventSynchronize(s->pipe.ev[slot]));
+    return *s->pipe.err[slot];
+}
+void gg::pipe_collect(gg_solver *s, int executed)
+{
+    std::vector<size_t> &ends = s->pipe.mark_ends;
+    const size_t upto = ends.empty() ? s->marks.size() : ends.front();
+    prof_collect(s, executed, upto);
+    if (!ends.empty()) {
+        ends.erase(ends.begin());
+        for (size_t &e : ends) e -= upto;
+    }
+}
+void gg::pipe_drain(gg_solver *s)
+{
+    GG_HIP(hipStreamSynchronize(s->st));
+    while (!s->pipe.mark_ends.empty()) pipe_collect(s, 0);
+    prof_collect(s, 0);
+}
+void gg::pipe_release(gg_solver *s)
+{
+    ReadPipe &p = s->pipe;
+    for (int k = 0; k < 2; k++) {
+        if (p.state[k]) (void)hipHostFree(p.state[k]);
+        if (p.err[k]) (void)hipHostFree(p.err[k]);
+        if (p.ev[k]) (void)hipEventDestroy(p.ev[k]);
+        p.state[k] = nullptr;
+        p.err[k] = nullptr;
+        p.ev[k] = nullptr;
+    }
 }
 
 namespace {
 
-// the control block and the error word in one round trip (after a cycle)
+// the control block and the error word in one round trip (after a cycle), with
+// nothing posted: slot 0 of the pipe
 DevState read_state_checked(gg_solver *s)
 {
-    if (!s->h_state) {
-        GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_state), sizeof(DevState), hipHostMallocDefault));
-        GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_err), sizeof(int), hipHostMallocDefault));
-    }
-    GG_HIP(hipMemcpyAsync(s->h_state, s->ds.p, sizeof(DevState), hipMemcpyDeviceToHost, s->st));
-    GG_HIP(hipMemcpyAsync(s->h_err, s->err.p, sizeof(int), hipMemcpyDeviceToHost, s->st));
-    GG_HIP(hipStreamSynchronize(s->st));
-    const int err = *s->h_err;
-    if (err & 8) throw Fallback{err};
-    GG_REQUIRE((err & 1) == 0, GG_ETIMEOUT, "wavefront triangular solve: boundary wait timed out");
-    if (err & 2) throw Fallback{err};
-    return *s->h_state;
+    pipe_post(s, 0, s->ds.p, sizeof(DevState), false);
+    raise_err(pipe_wait(s, 0));
+    return pipe_state<DevState>(s, 0);
 }
 // for the rest of the solver's life: every WD_RCP triangle divides (bit 1),
 // every 3D tile triangle claims its tiles from the queue (bit 3)
@@ -1451,33 +1501,11 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
     // at a time.
     const char *pe = std::getenv("GG_CYCLE_PIPE");
     const bool pipe = !(pe && pe[0] == '0') && !user_kind(s) && opt->max_iter >= 1;
+    pipe_begin(s);
     if (pipe) {
-        for (int k = 0; k < 2; k++)
-            if (!s->p_state[k]) {
-                GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->p_state[k]), sizeof(DevState), hipHostMallocDefault));
-                GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->p_err[k]), sizeof(int), hipHostMallocDefault));
-                GG_HIP(hipEventCreateWithFlags(&s->p_ev[k], hipEventDisableTiming));
-            }
-        s->mark_ends.clear();
         auto enqueue = [&](int slot) {          // one cycle and the read of the state after it
             enqueue_cycle(s, m);
-            s->mark_ends.push_back(s->marks.size());
-            GG_HIP(hipMemcpyAsync(s->p_state[slot], s->ds.p, sizeof(DevState), hipMemcpyDeviceToHost, s->st));
-            GG_HIP(hipMemcpyAsync(s->p_err[slot], s->err.p, sizeof(int), hipMemcpyDeviceToHost, s->st));
-            GG_HIP(hipEventRecord(s->p_ev[slot], s->st));
-        };
-        auto collect = [&](int executed) {      // the oldest enqueued cycle's marks
-            const size_t upto = s->mark_ends.empty() ? s->marks.size() : s->mark_ends.front();
-            prof_collect(s, executed, upto);
-            if (!s->mark_ends.empty()) {
-                s->mark_ends.erase(s->mark_ends.begin());
-                for (size_t &e : s->mark_ends) e -= upto;
-            }
-        };
-        auto drain = [&]() {                    // the speculative cycle behind the last (gated off)
-            GG_HIP(hipStreamSynchronize(s->st));
-            while (!s->mark_ends.empty()) collect(0);
-            prof_collect(s, 0);
+            pipe_post(s, slot, s->ds.p, sizeof(DevState));
         };
         // cycle 1 is gated on DONE_INIT (converged at the start) like the rest.
         // The transient loop's hint (the previous step's inner iterations, h):
@@ -1491,18 +1519,13 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
         if (hint > 0 && hint + 2 < m) {
             const int K = hint + 2;
             enqueue_cycle(s, m, 0, K, false);
-            GG_HIP(hipMemcpyAsync(s->p_state[0], s->ds.p, sizeof(DevState), hipMemcpyDeviceToHost, s->st));
-            GG_HIP(hipMemcpyAsync(s->p_err[0], s->err.p, sizeof(int), hipMemcpyDeviceToHost, s->st));
-            GG_HIP(hipEventRecord(s->p_ev[0], s->st));
-            GG_HIP(hipEventSynchronize(s->p_ev[0]));
-            const DevState hp = *s->p_state[0];
-            const bool conv = *s->p_err[0] == 0 && (hp.done & (DONE_INIT | DONE_INNER)) != 0 &&
+            pipe_post(s, 0, s->ds.p, sizeof(DevState), false);      // mid-cycle: its marks stay open
+            const int errp = pipe_wait(s, 0);
+            const DevState hp = pipe_state<DevState>(s, 0);
+            const bool conv = errp == 0 && (hp.done & (DONE_INIT | DONE_INNER)) != 0 &&
                               (hp.done & DONE_ABORT) == 0;
             enqueue_cycle(s, m, conv ? m : K, m, true);
-            s->mark_ends.push_back(s->marks.size());
-            GG_HIP(hipMemcpyAsync(s->p_state[0], s->ds.p, sizeof(DevState), hipMemcpyDeviceToHost, s->st));
-            GG_HIP(hipMemcpyAsync(s->p_err[0], s->err.p, sizeof(int), hipMemcpyDeviceToHost, s->st));
-            GG_HIP(hipEventRecord(s->p_ev[0], s->st));
+            pipe_post(s, 0, s->ds.p, sizeof(DevState));
             if (!conv) enqueue(1);
         } else {
             enqueue(0);
@@ -1513,31 +1536,21 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
         prev.j = 1;
         prev.hist_len = 1;
         while (true) {
-            GG_HIP(hipEventSynchronize(s->p_ev[cur]));
-            const int err = *s->p_err[cur];
-            DevState h = *s->p_state[cur];
-            if (err & 8) {
-                drain();
-                throw Fallback{err};
-            }
-            if (err & 1) {
-                drain();
-                GG_REQUIRE(false, GG_ETIMEOUT, "wavefront triangular solve: boundary wait timed out");
-            }
-            if (err & 2) {
-                drain();
-                throw Fallback{err};
+            const int err = pipe_wait(s, cur);
+            DevState h = pipe_state<DevState>(s, cur);
+            if (err & kErrSolve) {
+                pipe_drain(s);
+                raise_err(err);
             }
             if (h.done & DONE_ABORT) {
                 // this cycle aborted, the one behind it ran gated off: rerun this
                 // one on the per-step kernels, then refill the pipeline
-                drain();
+                pipe_drain(s);
                 h = rerun_aborted_cycle(s, m, h);
                 prof_collect(s, (h.done & DONE_INNER) ? h.conv_i + 1 : h.nit);   // the rerun's marks
-                s->mark_ends.clear();
                 enqueue(cur ^ 1);
             } else {
-                collect((h.done & DONE_INNER) ? h.conv_i + 1 : (h.done & DONE_INIT) ? 0 : h.nit);
+                pipe_collect(s, (h.done & DONE_INNER) ? h.conv_i + 1 : (h.done & DONE_INIT) ? 0 : h.nit);
             }
             relres = h.resid;
             if (h.done & DONE_INIT) {
@@ -1570,7 +1583,7 @@ int solve_device_once(gg_solver *s, const double *d_b, double *d_x, const gg_opt
             enqueue(cur);                       // the cycle after the one in flight
             cur ^= 1;
         }
-        drain();
+        pipe_drain(s);
     } else {
     // The first cycle goes in before the state after the initial residual is
     // read: its kernels are gated on DONE_INIT (converged at the start), so a
@@ -1752,15 +1765,7 @@ int gg_destroy(gg_solver *s)
     for (hipEvent_t e : s->prof_pool) (void)hipEventDestroy(e);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     gg::batch_release(s);
-    gg::cg_release(s);
-    gg::bicgstab_release(s);
-    if (s->h_state) (void)hipHostFree(s->h_state);
-    if (s->h_err) (void)hipHostFree(s->h_err);
-    for (int k = 0; k < 2; k++) {
-        if (s->p_state[k]) (void)hipHostFree(s->p_state[k]);
-        if (s->p_err[k]) (void)hipHostFree(s->p_err[k]);
-        if (s->p_ev[k]) (void)hipEventDestroy(s->p_ev[k]);
-    }
+    gg::pipe_release(s);
     hipStream_t st = s->st;
     delete s;
     if (st) (void)hipStreamDestroy(st);

@@ -31,7 +31,7 @@ from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 BI = ggmres.SOLVE_BICGSTAB
-CHUNK = 16                      # csrc/bicgstab.hip kChunk
+CHUNK = 16                      # csrc/bicgstab.hip BiCgStab::kChunk
 TOL = 1e-12
 
 
