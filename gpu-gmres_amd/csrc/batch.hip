@@ -125,6 +125,7 @@ void batch_release(gg_solver *s)
 {
     delete s->batch;
     s->batch = nullptr;
+    cg_batch_release(s);
 }
 
 namespace {
@@ -577,6 +578,7 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
     GG_REQUIRE(opt->flags == 0, GG_EINVAL, "gg_solve_batch: no flags are defined for the batch");
     GG_REQUIRE(ldb >= s->A.n && ldx >= s->A.n, GG_EINVAL, "gg_solve_batch: leading dimension below n");
     GG_HIP(hipSetDevice(s->device));
+    s->batch_last_cg = false;
     if (!batchable(s)) return solve_batch_seq(s, S, d_b, ldb, d_x, ldx, opt, res);
     for (int attempt = 0;; attempt++) {
         try {
@@ -602,6 +604,7 @@ bool batch_engine_on(gg_solver *s) { return batchable(s); }
 
 long long batch_history(gg_solver *s, int q, double *out, long long cap)
 {
+    if (s->batch_last_cg) return cg_batch_history(s, q, out, cap);
     BatchWs *B = s->batch;
     GG_REQUIRE(B && q >= 0 && q < B->S && B->hist_len[q] > 0, GG_ESTATE,
                "gg_batch_history: no batched solve holds that scenario");
@@ -689,6 +692,20 @@ int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const doubl
                        int *iters_total)
 {
     GG_BAPI_BEGIN
+    return transient_batch(s, false, nrhs, nsteps, h, cdiag, src_off, src_node, src_kind, src_ptr, src_data, nport,
+                           port, x, opt, port_out, iters_total);
+    GG_BAPI_END
+}
+
+}  // extern "C"
+
+// the transient loop of every scenario (gg_transient_batch; cg: gg_transient_cg_batch,
+// the step solved by solve_cg_batch with its first chunk sized by the previous step)
+int gg::transient_batch(gg_solver *s, bool cg, int nrhs, int nsteps, double h, const double *cdiag,
+                        const int *src_off, const int *src_node, const int *src_kind, const int *src_ptr,
+                        const double *src_data, int nport, const int *port, double *x, const gg_options *opt,
+                        double *port_out, int *iters_total)
+{
     GG_REQUIRE(s && opt && x && cdiag && src_off && iters_total, GG_EINVAL, "null argument");
     GG_REQUIRE(s->have_A, GG_ESTATE, "gg_transient_batch: no matrix");
     GG_REQUIRE(nrhs >= 1 && nsteps >= 0 && nport >= 0, GG_EINVAL, "gg_transient_batch: bad count");
@@ -746,13 +763,24 @@ int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const doubl
     std::vector<gg_result> res(nrhs);
     std::vector<long long> tot(nrhs, 0);
     int status = GG_OK;
+    struct HintReset {
+        gg_solver *s;
+        ~HintReset() { s->batch_iter_hint = 0; }
+    } hint_reset{s};
+    s->batch_iter_hint = 0;
     for (int it = 1; it <= nsteps; it++) {
         launch_transient_step_b(n, nrhs, maxsrc, d_soff.p, d_kind.p, d_dptr.p, d_data.p, it, h, d_u.p, d_sptr.p,
                                 d_sidx.p, d_c.p, d_x.p, d_w.p, n, st);
-        const int rc = solve_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data());
+        const int rc = cg ? solve_cg_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data())
+                          : solve_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data());
         if (rc < 0) return rc;
         if (rc) status = rc;
         for (int q = 0; q < nrhs; q++) tot[q] += res[q].iters;
+        if (cg) {
+            int mx = 0;
+            for (int q = 0; q < nrhs; q++) mx = std::max(mx, res[q].inner_iters);
+            s->batch_iter_hint = mx;
+        }
         launch_gather_ports_b(nport, d_port.p, d_x.p, n, d_pv.p + (long long)it * nport, ldo, nrhs, st);
     }
     if (nport) {
@@ -768,7 +796,4 @@ int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const doubl
     GG_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < nrhs; q++) iters_total[q] = (int)std::min<long long>(tot[q], INT32_MAX);
     return status;
-    GG_BAPI_END
 }
-
-}  // extern "C"

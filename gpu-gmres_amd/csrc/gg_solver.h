@@ -19,6 +19,20 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
                 const gg_options *opt, gg_result *res);
 bool batch_engine_on(gg_solver *s);
 long long batch_history(gg_solver *s, int q, double *out, long long cap);
+// cg_batch.hip: the many-RHS conjugate-gradient engine behind
+// gg_solve_cg_batch_device (also the CG transient batch's step), its
+// per-scenario histories (batch_history hands over when the last batch ran
+// CG: s->batch_last_cg) and its work space
+struct CgBatchWs;
+int solve_cg_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d_x, long long ldx,
+                   const gg_options *opt, gg_result *res);
+long long cg_batch_history(gg_solver *s, int q, double *out, long long cap);
+void cg_batch_release(gg_solver *s);
+// batch.hip: the body of gg_transient_batch and gg_transient_cg_batch (cg: the
+// step solver is solve_cg_batch, its first chunk sized by the previous step)
+int transient_batch(gg_solver *s, bool cg, int nrhs, int nsteps, double h, const double *cdiag, const int *src_off,
+                    const int *src_node, const int *src_kind, const int *src_ptr, const double *src_data, int nport,
+                    const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total);
 // cg.hip, bicgstab.hip: the GG_SOLVE_CG and GG_SOLVE_BICGSTAB engines behind
 // solve_device (arguments checked by the caller, s->shared set); both are
 // short_recurrence.h's driver over their own launches
@@ -176,6 +190,12 @@ struct gg_solver {
     // the many-RHS solve's per-scenario arenas (batch.hip), kept between
     // batched solves of the same shape
     gg::BatchWs *batch = nullptr;
+    // the CG batch's (cg_batch.hip); batch_last_cg: gg_batch_history reads it;
+    // batch_iter_hint: the CG transient batch's previous step, the largest
+    // count of its scenarios (0: none)
+    gg::CgBatchWs *cg_batch = nullptr;
+    bool batch_last_cg = false;
+    int batch_iter_hint = 0;
 };
 
 namespace gg {

@@ -434,5 +434,21 @@ void launch_update_b(Gate g, int m, DevState *ds, const double *H, const double 
                      long long ldv, double *acc, int G, long long Ppad, const UnitMap &um, int nsc, long long zs,
                      hipStream_t st);
 void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, int nsc, long long zs, hipStream_t st);
+// the CG launches for nsc scenarios (cg_batch.hip): the kernels of launch_normb
+// and launch_cg_* on a grid (G, nsc), the control block, history and partials
+// per scenario like the vectors; the gate's done / nit = scenario 0's words
+void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st);
+// out[q] = scenario q's control block, q < nsc; *err_out = *err
+void launch_pack_cg_states_b(const CgState *cs, long long zs, int nsc, CgState *out, const int *err, int *err_out,
+                             hipStream_t st);
+void launch_normb_b(const double *part, int G, double *normb, int nsc, long long zs, hipStream_t st);
+void launch_cg_pq_b(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, int nsc,
+                    long long zs, hipStream_t st);
+void launch_cg_xr_b(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
+                    const double *q, long long Ppad, int nsc, long long zs, hipStream_t st);
+void launch_cg_rz_b(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, int nsc,
+                    long long zs, hipStream_t st);
+void launch_cg_p_b(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
+                   double *hist, long long Ppad, int nsc, long long zs, hipStream_t st);
 
 }  // namespace gg

@@ -3298,6 +3298,25 @@ __global__ void k_pack_states_b(const DevState *ds, long long zs, int nsc, DevSt
     if (q < nsc) out[q] = *zp(ds, zs, q);
     if (q == nsc) out[nsc].err = *err;          // the error word after every launch before this one
 }
+// the same for the CG batch's control blocks (cg_batch.hip): every scenario's
+// CgState at the start of a solve; all of them and the error word (*err_out)
+// into a read-back slot
+__global__ void k_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nsc) return;
+    CgState h{};
+    h.tol = tol;
+    h.max_iter = max_iter;
+    *zp(cs, zs, q) = h;
+}
+__global__ void k_pack_cg_states_b(const CgState *cs, long long zs, int nsc, CgState *out, const int *err,
+                                   int *err_out)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nsc) out[q] = *zp(cs, zs, q);
+    if (q == nsc) *err_out = *err;
+}
 // transient step of every scenario: u_sc = its sources at time index it; w_sc
 // = B_sc u_sc + (C/h) x_sc (k_sources + k_transient_rhs per scenario; tables
 // concatenated, scenario sc's sources [soff[sc], soff[sc+1]) and its B^T rows
@@ -5132,8 +5151,14 @@ __global__ void k_end_cycle(const double *part, int G, DevState *ds, double *his
 // (every block forms the same scalars).  rz alternates between two words: the
 // launch that forms iteration it's beta from rz[it & 1] stores the next one.
 // (k_normb, k_cg_pq and k_cg_rz touch no control block: BiCGStab launches them too.)
-__global__ void k_normb(const double *part, int G, double *normb)
+// zs: the many-RHS batch (cg_batch.hip), as k_dot -- grid (G, nsc), blockIdx.y
+// = scenario, every per-scenario pointer (vectors, partials, control block,
+// history, the gate's words) blockIdx.y * zs bytes on; the control block is
+// then written by thread 0 of block (0, scenario).  zs = 0: the single solve.
+__global__ void k_normb(const double *part, int G, double *normb, long long zs = 0)
 {
+    part = zp(part, zs, blockIdx.y);
+    normb = zp(normb, zs, blockIdx.y);
     const double s = sum_partials(part, G);
     if (threadIdx.x == 0) {
         const double nb = sqrt(s);
@@ -5143,9 +5168,13 @@ __global__ void k_normb(const double *part, int G, double *normb)
 
 // block partials of p . q
 __global__ __launch_bounds__(kBlock) void k_cg_pq(Gate g, const double *__restrict__ p,
-                                                  const double *__restrict__ q, double *part, long long units)
+                                                  const double *__restrict__ q, double *part, long long units,
+                                                  long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    p = zp(p, zs, blockIdx.y);
+    q = zp(q, zs, blockIdx.y);
+    part = zp(part, zs, blockIdx.y);
     double acc = 0.0;
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x; u0 < units; u0 += kUnroll * stride) {
@@ -5172,9 +5201,15 @@ __global__ __launch_bounds__(kBlock) void k_cg_pq(Gate g, const double *__restri
 __global__ __launch_bounds__(kBlock) void k_cg_xr(Gate g, int it, CgState *cs, const double *part, int G,
                                                   double *__restrict__ x, const double *__restrict__ p,
                                                   double *__restrict__ r, const double *__restrict__ q,
-                                                  long long units)
+                                                  long long units, long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    cs = zp(cs, zs, blockIdx.y);
+    part = zp(part, zs, blockIdx.y);
+    x = zp(x, zs, blockIdx.y);
+    p = zp(p, zs, blockIdx.y);
+    r = zp(r, zs, blockIdx.y);
+    q = zp(q, zs, blockIdx.y);
     const long long stride = (long long)gridDim.x * kBlock;
     long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
     double2 xv[kUnroll], pv[kUnroll], rv[kUnroll], qv[kUnroll];
@@ -5221,9 +5256,13 @@ __global__ __launch_bounds__(kBlock) void k_cg_xr(Gate g, int it, CgState *cs, c
 
 // block partials of r . z (part[b]) and z . z (part[G + b]) in one pass
 __global__ __launch_bounds__(kBlock) void k_cg_rz(Gate g, const double *__restrict__ r,
-                                                  const double *__restrict__ z, double *part, long long units)
+                                                  const double *__restrict__ z, double *part, long long units,
+                                                  long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    r = zp(r, zs, blockIdx.y);
+    z = zp(z, zs, blockIdx.y);
+    part = zp(part, zs, blockIdx.y);
     double acc[2] = {0.0, 0.0};
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x; u0 < units; u0 += kUnroll * stride) {
@@ -5253,9 +5292,14 @@ __global__ __launch_bounds__(kBlock) void k_cg_rz(Gate g, const double *__restri
 template <bool START>
 __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, const double *part, int G,
                                                  double *__restrict__ p, const double *__restrict__ z,
-                                                 double *hist, long long units)
+                                                 double *hist, long long units, long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    cs = zp(cs, zs, blockIdx.y);
+    part = zp(part, zs, blockIdx.y);
+    p = zp(p, zs, blockIdx.y);
+    z = zp(z, zs, blockIdx.y);
+    hist = zp(hist, zs, blockIdx.y);
     const long long stride = (long long)gridDim.x * kBlock;
     long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
     double2 pv[kUnroll], zv[kUnroll];
@@ -6649,6 +6693,40 @@ void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, i
 }
 
 // ---- CG (cg.hip) ----------------------------------------------------------------
+void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st)
+{
+    k_init_cg_state_b<<<(nsc + 63) / 64, 64, 0, st>>>(cs, zs, nsc, tol, max_iter);
+}
+void launch_pack_cg_states_b(const CgState *cs, long long zs, int nsc, CgState *out, const int *err, int *err_out,
+                             hipStream_t st)
+{
+    k_pack_cg_states_b<<<(nsc + 64) / 64, 64, 0, st>>>(cs, zs, nsc, out, err, err_out);
+}
+void launch_normb_b(const double *part, int G, double *normb, int nsc, long long zs, hipStream_t st)
+{
+    k_normb<<<dim3(1, nsc), kBlock, 0, st>>>(part, G, normb, zs);
+}
+void launch_cg_pq_b(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, int nsc,
+                    long long zs, hipStream_t st)
+{
+    k_cg_pq<<<dim3(G, nsc), kBlock, 0, st>>>(g, p, q, part, Ppad / 2, zs);
+}
+void launch_cg_xr_b(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
+                    const double *q, long long Ppad, int nsc, long long zs, hipStream_t st)
+{
+    k_cg_xr<<<dim3(G, nsc), kBlock, 0, st>>>(g, it, cs, part, G, x, p, r, q, Ppad / 2, zs);
+}
+void launch_cg_rz_b(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, int nsc,
+                    long long zs, hipStream_t st)
+{
+    k_cg_rz<<<dim3(G, nsc), kBlock, 0, st>>>(g, r, z, part, Ppad / 2, zs);
+}
+void launch_cg_p_b(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
+                   double *hist, long long Ppad, int nsc, long long zs, hipStream_t st)
+{
+    if (start) k_cg_p<true><<<dim3(G, nsc), kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, zs);
+    else k_cg_p<false><<<dim3(G, nsc), kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, zs);
+}
 void launch_normb(const double *part, int G, double *normb, hipStream_t st)
 {
     k_normb<<<1, kBlock, 0, st>>>(part, G, normb);

@@ -2390,7 +2390,7 @@ static int transient_loop(gg_solver *s, int it0, int nsteps, double h, const dou
     }
     d_kind.upload(kind.data(), kind.size(), s->st);
     d_dptr.upload(dptr.data(), dptr.size(), s->st);
-    d_data.upload(data.data(), std::max<size_t>(data.size(), 1), s->st);
+    d_data.upload(data.data(), data.size(), s->st);      // (no sources: one element, nothing copied)
     d_u.alloc(std::max(nsrc, 1));
     d_w.alloc(std::max(n, 1));
     d_port.upload(port, nport, s->st);

@@ -41,6 +41,7 @@ EXPORTS = [
     "gg_device_fingerprint", "gg_set_matrix_count", "gg_trsv_levels", "gg_layout", "gg_reduce_blocks",
     "gg_solve_batch_device", "gg_solve_batch", "gg_batch_engine", "gg_batch_history", "gg_transient_batch",
     "gg_set_precond_ainv", "gg_set_precond_diag", "gg_ainv_fused", "gg_ainv_nnz", "gg_ainv_sliced",
+    "gg_solve_cg_batch_device", "gg_solve_cg_batch", "gg_transient_cg_batch",
 ]
 # gg_precond_fn: int (*)(void *ctx, int op, const float *in, float *out, int n), device arrays
 PRECOND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -157,6 +158,9 @@ def lib():
         L.gg_batch_history.restype = ctypes.c_longlong
         L.gg_transient_batch.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_double, _D, _I, _I, _I, _I, _D,
                                          ctypes.c_int, _I, _D, ctypes.POINTER(Options), _D, _I]
+        L.gg_solve_cg_batch_device.argtypes = L.gg_solve_batch_device.argtypes
+        L.gg_solve_cg_batch.argtypes = L.gg_solve_batch.argtypes
+        L.gg_transient_cg_batch.argtypes = L.gg_transient_batch.argtypes
         L.gg_profile_enable.argtypes = [_VP, ctypes.c_int]
         L.gg_profile_reset.argtypes = [_VP]
         L.gg_profile_get.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
@@ -395,13 +399,15 @@ class Solver:
         """nrhs independent solves A x_q = b_q (rows of B), batched; returns
         dict(x [nrhs, n], iters / inner / restarts / relres / status per
         scenario, hist = per-scenario histories)."""
+        return self._solve_batch(lib().gg_solve_batch, B, X0, restart, max_iter, tol, flags)
+
+    def _solve_batch(self, fn, B, X0, restart, max_iter, tol, flags):
         B = np.ascontiguousarray(np.atleast_2d(B), np.float64)
         S, n = B.shape
         X = np.zeros((S, n)) if X0 is None else np.array(np.atleast_2d(X0), np.float64, copy=True, order="C")
         o = Options(int(restart), int(max_iter), float(tol), int(flags))     # (the batch defines no flags)
         res = (Result * S)()
-        rc = _check(lib().gg_solve_batch(self.h, S, B.reshape(-1), n, X.reshape(-1), n, ctypes.byref(o), res),
-                    allow_nc=True)
+        rc = _check(fn(self.h, S, B.reshape(-1), n, X.reshape(-1), n, ctypes.byref(o), res), allow_nc=True)
         out = self._batch_out(rc, res)
         out["x"] = X
         out["hist"] = [self.batch_history(q) for q in range(S)]
@@ -414,6 +420,21 @@ class Solver:
         res = (Result * int(nrhs))()
         rc = _check(lib().gg_solve_batch_device(self.h, int(nrhs), _VP(b_ptr), ld, _VP(x_ptr), ld,
                                                 ctypes.byref(o), res), allow_nc=True)
+        return self._batch_out(rc, res)
+
+    def solve_cg_batch(self, B, X0=None, max_iter=3000, tol=1e-10, flags=SOLVE_CG):
+        """solve_batch by conjugate gradients (gg_solve_cg_batch; A and M SPD):
+        the same dict, scenario q bit-identical to solve(B[q], flags=SOLVE_CG);
+        ret EBREAKDOWN when a scenario broke down (status per scenario)"""
+        return self._solve_batch(lib().gg_solve_cg_batch, B, X0, 30, max_iter, tol, flags)
+
+    def solve_cg_batch_device(self, b_ptr, x_ptr, nrhs, ld=None, max_iter=3000, tol=1e-10, flags=SOLVE_CG):
+        """solve_batch_device by conjugate gradients (gg_solve_cg_batch_device)"""
+        ld = self.n if ld is None else int(ld)
+        o = Options(30, int(max_iter), float(tol), int(flags))
+        res = (Result * int(nrhs))()
+        rc = _check(lib().gg_solve_cg_batch_device(self.h, int(nrhs), _VP(b_ptr), ld, _VP(x_ptr), ld,
+                                                   ctypes.byref(o), res), allow_nc=True)
         return self._batch_out(rc, res)
 
     def batch_history(self, q):
@@ -431,6 +452,16 @@ class Solver:
         = [(kind, params), ...] (as transient_src) or a PULSE parameter array
         (n_src x 7); X0 [nrhs, n].  Returns dict(x [nrhs, n], ports [nrhs, nport,
         nsteps+1], iters_total [nrhs], ret)."""
+        return self._transient_batch(lib().gg_transient_batch, nsteps, h, cdiag, scenarios, ports, X0, restart,
+                                     max_iter, tol)
+
+    def transient_cg_batch(self, nsteps, h, cdiag, scenarios, ports, X0, restart=32, max_iter=10000, tol=1e-7):
+        """transient_batch with every step solved by conjugate gradients
+        (gg_transient_cg_batch; A = G + C/h SPD): the same arguments and result"""
+        return self._transient_batch(lib().gg_transient_cg_batch, nsteps, h, cdiag, scenarios, ports, X0, restart,
+                                     max_iter, tol)
+
+    def _transient_batch(self, fn, nsteps, h, cdiag, scenarios, ports, X0, restart, max_iter, tol):
         S = len(scenarios)
         X = np.array(np.atleast_2d(X0), np.float64, copy=True, order="C")
         assert X.shape == (S, self.n)
@@ -453,10 +484,9 @@ class Solver:
         tot = np.zeros(S, np.int32)
         o = Options(int(restart), int(max_iter), float(tol), 0)
         one = np.zeros(1, np.int32)
-        rc = _check(lib().gg_transient_batch(self.h, S, int(nsteps), float(h), np.ascontiguousarray(cdiag, np.float64),
-                                             np.array(off, np.int32), node, kind, ptr, data, len(ports),
-                                             ports if len(ports) else one, X.reshape(-1), ctypes.byref(o), pv, tot),
-                    allow_nc=True)
+        rc = _check(fn(self.h, S, int(nsteps), float(h), np.ascontiguousarray(cdiag, np.float64),
+                       np.array(off, np.int32), node, kind, ptr, data, len(ports),
+                       ports if len(ports) else one, X.reshape(-1), ctypes.byref(o), pv, tot), allow_nc=True)
         return dict(x=X, ports=pv[: S * len(ports) * (nsteps + 1)].reshape(S, len(ports), nsteps + 1),
                     iters_total=[int(t) for t in tot], ret=rc)
 

@@ -128,8 +128,11 @@ typedef struct gg_options {
  * gg_transient* loops (warm start as with GMRES), with GG_PRECOND_NONE, DIAG,
  * AINV, ILU0, ILUK or LU (host- or device-factored, any triangular-solve
  * path); GG_EINVAL with GG_PRECOND_SPLIT / USER / USER_SPLIT and in
- * gg_solve_batch*.  May be combined with GG_SOLVE_SHARED_DEVICE under that
- * flag's own conditions (the CG kernels wait on nothing).
+ * gg_solve_batch* and gg_transient_batch, which define no flags: many
+ * right-hand sides are solved by CG through entry points of their own,
+ * gg_solve_cg_batch_device, gg_solve_cg_batch and gg_transient_cg_batch (the
+ * many-RHS section below).  May be combined with GG_SOLVE_SHARED_DEVICE under
+ * that flag's own conditions (the CG kernels wait on nothing).
  * GG_EBREAKDOWN: p.Ap is not > 0, or r.Mr is not > 0 while the solve has not
  * converged (NaN counts as not > 0) -- how a matrix or preconditioner that is
  * not SPD shows.  x then holds the last iterate, res->status the code. */
@@ -487,6 +490,37 @@ int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const doubl
                        const int *src_node, const int *src_kind, const int *src_ptr, const double *src_data,
                        int nport, const int *port, double *x, const gg_options *opt, double *port_out,
                        int *iters_total);
+/* The many-RHS solve by conjugate gradients (cg_batch.hip): gg_solve_batch*
+ * with GG_SOLVE_CG's method.  nrhs, ldb, ldx, the warm start in x and res[q]
+ * as above.  opt->flags is GG_SOLVE_CG or 0 -- both mean CG, the entry point
+ * names the method -- and any other bit GG_EINVAL; opt->restart is validated
+ * in [1, 512] and otherwise ignored; opt->max_iter bounds each scenario's
+ * iterations.  Preconditioners as for GG_SOLVE_CG (GG_EINVAL with
+ * GG_PRECOND_SPLIT / USER / USER_SPLIT).  Scenario q is exactly the single CG
+ * solve: status, iteration count, relres, history (gg_batch_history: the
+ * initial value, then one entry per iteration) and solution bits equal those
+ * of gg_solve_device(GG_SOLVE_CG) on that right-hand side alone; res[q]:
+ * iters = inner_iters = its iterations, restarts = 0, status GG_OK,
+ * GG_NOT_CONVERGED or GG_EBREAKDOWN.  Batched when gg_batch_engine() = 1:
+ * per iteration one SpMV, four CG launches and the two wavefront triangular
+ * solves for all scenarios, a scenario that is over dropping out of them.
+ * Otherwise the scenarios are solved one after the other by the single CG
+ * solve, with the same results.  A scenario that breaks down stops, the
+ * others run to their own end.  Returns GG_EBREAKDOWN if any scenario broke
+ * down (gg_last_error names the first one and its iteration), else 1 if any
+ * did not converge, else GG_OK; other values < 0 on error.  x holds every
+ * scenario's last iterate. */
+int gg_solve_cg_batch_device(gg_solver *s, int nrhs, const double *d_b, long long ldb, double *d_x, long long ldx,
+                             const gg_options *opt, gg_result *res);
+int gg_solve_cg_batch(gg_solver *s, int nrhs, const double *b, long long ldb, double *x, long long ldx,
+                      const gg_options *opt, gg_result *res);   /* host arrays */
+/* gg_transient_batch with every step solved by gg_solve_cg_batch_device (A =
+ * G + C/h symmetric positive definite): the same arguments and results; a
+ * step's first chunk of iterations is sized by the previous step's counts. */
+int gg_transient_cg_batch(gg_solver *s, int nrhs, int nsteps, double h, const double *cdiag, const int *src_off,
+                          const int *src_node, const int *src_kind, const int *src_ptr, const double *src_data,
+                          int nport, const int *port, double *x, const gg_options *opt, double *port_out,
+                          int *iters_total);
 
 /* Diagnostics: run one wavefront triangular solve (which: 0 = L / Ml, 1 = U / Mr)
  * on the current right-hand side and return, per band, the device real-time
