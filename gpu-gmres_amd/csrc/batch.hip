@@ -35,6 +35,7 @@
 #include <type_traits>
 #include <climits>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -111,6 +112,10 @@ struct BatchWs {
     DevState *d_st[kSlots] = {};
     hipEvent_t ev[kSlots] = {};
     std::vector<long long> hist_len;     // per scenario, of the last batched solve
+    // the orthogonalization the last batched solve ran to its end with
+    // (gg_batch_mgs_kernel): 2 k_arnoldi_persist2 (an odd last scenario on
+    // k_arnoldi_persist), 1 k_arnoldi_persist per scenario, 0 the per-step kernels
+    int ran_mgs = -1;
     double *dp(long long off) { return reinterpret_cast<double *>(arena.p + off); }
     ~BatchWs()
     {
@@ -196,7 +201,7 @@ void ensure_batch(gg_solver *s, int S, int m, long long hist_need)
     B->oUg = take(B->ngU * 8);
     {
         const int pj = arnoldi_persist_units(s->G, s->Ppad);
-        const int xr = (mgs_gather_form() == 3 && mgs_prefetch()) ? kMgsXcds : 0;
+        const int xr = pj ? arnoldi_persist_extra(pj) : 0;
         B->persist = batch_mgs() == 1 && pj != 0 && s->G + xr <= arnoldi_persist_max_blocks(pj);
         B->persist2 = B->persist && S > 1 && xr == 0 && mgs_gather_form() == 2 && mgs_prefetch() == 1 &&
                       arnoldi_persist2_units(s->G, s->Ppad) != 0 && batch_mgs2();
@@ -361,6 +366,7 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
     const long long need = (long long)opt->max_iter + opt->max_iter / m + 4;
     ensure_batch(s, S, m, need);
     BatchWs *B = s->batch;
+    B->ran_mgs = -1;
     if (!s->err.p) s->err.alloc(1);
     Ctx c;
     c.s = s;
@@ -530,6 +536,7 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
     float ms = 0.f;
     GG_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     int rc = GG_OK;
+    B->ran_mgs = B->persist2 ? 2 : B->persist ? 1 : 0;
     for (int q = 0; q < S; q++) {
         const Track &t = tr[q];
         B->hist_len[q] = t.hist_len;
@@ -553,6 +560,7 @@ int solve_batch_seq(gg_solver *s, int S, const double *d_b, long long ldb, doubl
 {
     int rc = GG_OK;
     if (s->batch) s->batch->hist_len.assign(S, 0);
+    if (s->batch) s->batch->ran_mgs = -1;
     for (int q = 0; q < S; q++) {
         gg_result r{};
         const int e = solve_one(s, d_b + (long long)q * ldb, d_x + (long long)q * ldx, opt, &r);
@@ -601,6 +609,15 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
 }
 
 bool batch_engine_on(gg_solver *s) { return batchable(s); }
+
+std::string batch_mgs_kernel(gg_solver *s)
+{
+    const BatchWs *B = s->batch;
+    if (s->batch_last_cg || !B || B->ran_mgs <= 0) return "";
+    const int J = arnoldi_persist_units(s->G, s->Ppad);
+    if (B->ran_mgs == 2) return "k_arnoldi_persist2<" + std::to_string(J) + ">";
+    return arnoldi_persist_name(J);
+}
 
 long long batch_history(gg_solver *s, int q, double *out, long long cap)
 {
@@ -683,6 +700,16 @@ int gg_batch_engine(gg_solver *s)
     GG_REQUIRE(s, GG_EINVAL, "null solver");
     GG_REQUIRE(s->pkind >= 0, GG_ESTATE, "gg_batch_engine: no preconditioner");
     return batch_engine_on(s) ? 1 : 0;
+    GG_BAPI_END
+}
+
+int gg_batch_mgs_kernel(gg_solver *s, char *name, int cap)
+{
+    GG_BAPI_BEGIN
+    GG_REQUIRE(s && name && cap > 0, GG_EINVAL, "null argument");
+    const std::string k = batch_mgs_kernel(s);
+    std::snprintf(name, (size_t)cap, "%s", k.c_str());
+    return (int)k.size();
     GG_BAPI_END
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "kernels.h"
@@ -18,6 +19,7 @@ UnitMap solver_unit_map(const gg_solver *s);
 int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d_x, long long ldx,
                 const gg_options *opt, gg_result *res);
 bool batch_engine_on(gg_solver *s);
+std::string batch_mgs_kernel(gg_solver *s);     // gg_batch_mgs_kernel
 long long batch_history(gg_solver *s, int q, double *out, long long cap);
 // cg_batch.hip: the many-RHS conjugate-gradient engine behind
 // gg_solve_cg_batch_device (also the CG transient batch's step), its

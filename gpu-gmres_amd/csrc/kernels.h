@@ -295,6 +295,11 @@ constexpr int kMgsXcdWords = 8 * 16, kMgsElectWords = 8 * 16;
 constexpr int kMgsXcds = 8;          // XCDs (GG_MGS_GATHER 3: one reducer-only block each)
 int mgs_gather_form();   // GG_MGS_GATHER: 0 every block gathers, 2 XCD-local reducers, 3 reducer-only blocks
 int mgs_prefetch();      // GG_MGS_PREFETCH: 1 v_{k+1} streamed during the gather, 0 after it
+// rocprofv3 name of the instantiation launch_arnoldi_persist runs for J units
+// per thread under the current GG_MGS_GATHER / GG_MGS_PREFETCH (the launch's own
+// mapping: gather 3 without prefetch runs <J, 2, 0>, prefetch 2 at J = 8 <8, *, 1>)
+std::string arnoldi_persist_name(int J);
+int arnoldi_persist_extra(int J);    // blocks that instantiation takes beside the G (reducer-only: kMgsXcds or 0)
 void launch_arnoldi_persist(Gate g, int i, int m, DevState *ds, const double *w, double *V,
                             long long ldv, double *H, double *cs, double *sn, double *s,
                             double *hist, unsigned long long *gran, unsigned long long *hg, int G,

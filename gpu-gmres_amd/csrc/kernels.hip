@@ -6373,14 +6373,37 @@ PersistFn persist_fn_j(int J)
                         : k_arnoldi_persist<8, XG, PF>;
     }
 }
+// GG_MGS_GATHER / GG_MGS_PREFETCH onto the instantiation <J, XG, PF> that runs:
+// the one mapping behind the launch, the occupancy query, the reducer-only
+// blocks (arnoldi_persist_extra) and the name gg_mgs_kernel reports
+void persist_form(int J, int &xg, int &pf)
+{
+    const int g = mgs_gather_form(), p = mgs_prefetch();
+    if (g == 2 && p == 2 && J <= 4) xg = 2, pf = 2;
+    else if (g == 3 && p) xg = 3, pf = 1;
+    else if (g >= 2) xg = 2, pf = p ? 1 : 0;
+    else xg = 0, pf = p ? 1 : 0;
+}
 PersistFn persist_fn(int J)
 {
-    const int xg = mgs_gather_form();
-    const int pf = mgs_prefetch();
-    if (xg == 2 && pf == 2 && J <= 4) return persist_fn_j<2, 2>(J);
-    if (xg == 3 && pf) return persist_fn_j<3, 1>(J);
-    if (xg >= 2) return pf ? persist_fn_j<2, 1>(J) : persist_fn_j<2, 0>(J);
+    int xg, pf;
+    persist_form(J, xg, pf);
+    if (xg == 2 && pf == 2) return persist_fn_j<2, 2>(J);
+    if (xg == 3) return persist_fn_j<3, 1>(J);
+    if (xg == 2) return pf ? persist_fn_j<2, 1>(J) : persist_fn_j<2, 0>(J);
     return pf ? persist_fn_j<0, 1>(J) : persist_fn_j<0, 0>(J);
+}
+int arnoldi_persist_extra(int J)
+{
+    int xg, pf;
+    persist_form(J, xg, pf);
+    return xg == 3 ? kXcds : 0;       // <J, 3, 1>: one reducer-only block per XCD
+}
+std::string arnoldi_persist_name(int J)
+{
+    int xg, pf;
+    persist_form(J, xg, pf);
+    return "k_arnoldi_persist<" + std::to_string(J) + ", " + std::to_string(xg) + ", " + std::to_string(pf) + ">";
 }
 
 // blocks of the J-unit instantiation that can be resident at once
@@ -6451,7 +6474,7 @@ void launch_arnoldi_persist(Gate g, int i, int m, DevState *ds, const double *w,
     GG_REQUIRE(persist_np(J) == 0 || G <= persist_np(J) * kBlock, GG_EINVAL,
                "k_arnoldi_persist: grid beyond the all-gather's reach");
     const PersistFn f = persist_fn(J);
-    const int extra = (mgs_gather_form() == 3 && mgs_prefetch()) ? kXcds : 0;   // reducer-only blocks
+    const int extra = arnoldi_persist_extra(J);                                 // reducer-only blocks
     f<<<G + extra, kBlock, persist_test_lds(), st>>>(g, i, m, ds, w, V, ldv, H, cs, sn, s, hist, gran, hg, Ppad / 2,
                                                      err, xb, elect, seq, um, trace, msc, mout,
                                                      reinterpret_cast<unsigned long long *>(fill), fill ? nfill : 0);

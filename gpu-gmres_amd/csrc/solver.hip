@@ -806,7 +806,7 @@ void ensure_workspace(gg_solver *s, int m)
         const bool force_wide = wf && wf[0] == '1';
         const int pj = arnoldi_persist_units(s->G, s->Ppad);
         // (GG_MGS_GATHER 3: kXcds reducer-only blocks beside the G)
-        const int xr = (mgs_gather_form() == 3 && mgs_prefetch()) ? kMgsXcds : 0;
+        const int xr = pj ? arnoldi_persist_extra(pj) : 0;
         s->persist = !off && !force_wide && pj != 0 && s->G + xr <= arnoldi_persist_max_blocks(pj);
         s->wide = !off && !s->persist && arnoldi_wide_ok(s->G, s->Ppad);   // long vectors: w on chip
         if (s->persist || s->wide) s->gran.alloc((size_t)m * (m + 2) * (s->G + 1));
@@ -2297,10 +2297,16 @@ int gg_mgs_kernel(gg_solver *s, char *name, int cap)
     std::string k;
     if (s->m_alloc > 0 && !s->shared && !s->last_cg) {
         if (s->persist)
-            k = "k_arnoldi_persist<" + std::to_string(arnoldi_persist_units(s->G, s->Ppad)) + ", " +
-                std::to_string(mgs_gather_form()) + ", " + std::to_string(mgs_prefetch()) + ">";
+            k = arnoldi_persist_name(arnoldi_persist_units(s->G, s->Ppad));
         else if (s->wide) k = "k_arnoldi_wide";
     }
+    std::snprintf(name, (size_t)cap, "%s", k.c_str());
+    return (int)k.size();
+}
+int gg_mgs_kernel_for(int units, char *name, int cap)
+{
+    if ((units != 1 && units != 2 && units != 4 && units != 8) || !name || cap <= 0) return GG_EINVAL;
+    const std::string k = arnoldi_persist_name(units);
     std::snprintf(name, (size_t)cap, "%s", k.c_str());
     return (int)k.size();
 }

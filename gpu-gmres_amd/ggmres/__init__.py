@@ -41,7 +41,8 @@ EXPORTS = [
     "gg_device_fingerprint", "gg_set_matrix_count", "gg_trsv_levels", "gg_layout", "gg_reduce_blocks",
     "gg_solve_batch_device", "gg_solve_batch", "gg_batch_engine", "gg_batch_history", "gg_transient_batch",
     "gg_set_precond_ainv", "gg_set_precond_diag", "gg_ainv_fused", "gg_ainv_nnz", "gg_ainv_sliced",
-    "gg_solve_cg_batch_device", "gg_solve_cg_batch", "gg_transient_cg_batch",
+    "gg_solve_cg_batch_device", "gg_solve_cg_batch", "gg_transient_cg_batch", "gg_batch_mgs_kernel",
+    "gg_mgs_kernel_for",
 ]
 # gg_precond_fn: int (*)(void *ctx, int op, const float *in, float *out, int n), device arrays
 PRECOND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -103,6 +104,8 @@ def lib():
         L.gg_division_active.argtypes = [_VP, ctypes.c_int]
         L.gg_trsv_kernel.argtypes = [_VP, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.gg_mgs_kernel.argtypes = [_VP, ctypes.c_char_p, ctypes.c_int]
+        L.gg_batch_mgs_kernel.argtypes = [_VP, ctypes.c_char_p, ctypes.c_int]
+        L.gg_mgs_kernel_for.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.gg_set_precond_iluk_device.argtypes = [_VP, ctypes.c_int]
         _PI, _PD = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
         L.gg_iluk_device_factors.argtypes = [_VP, ctypes.c_int, _I, ctypes.POINTER(_PI), ctypes.POINTER(_PD),
@@ -388,6 +391,13 @@ class Solver:
     def batch_engine(self):
         """True when gg_solve_batch* runs batched launches (else scenario by scenario)"""
         return bool(_check(lib().gg_batch_engine(self.h), allow_nc=True))
+
+    def batch_mgs_kernel(self):
+        """rocprofv3 name of the last batched GMRES solve's one-launch
+        orthogonalization kernel ('' = the per-step kernels; gg_batch_mgs_kernel)"""
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().gg_batch_mgs_kernel(self.h, buf, 256))
+        return buf.value.decode()
 
     @staticmethod
     def _batch_out(rc, res):
@@ -695,6 +705,14 @@ class Solver:
         """bytes the triangular solve's kernel itself streams (no index arrays on
         the wavefront)"""
         return lib().gg_bytes_trsv_stream(self.h, int(which))
+
+
+def mgs_kernel_for(units):
+    """the k_arnoldi_persist instantiation for `units` units per thread under the
+    current GG_MGS_GATHER / GG_MGS_PREFETCH (gg_mgs_kernel_for; no device needed)"""
+    buf = ctypes.create_string_buffer(256)
+    _check(lib().gg_mgs_kernel_for(int(units), buf, 256))
+    return buf.value.decode()
 
 
 def device_count():

@@ -302,10 +302,15 @@ int gg_division_active(gg_solver *s, int which);
  * ("" when the preconditioner has no triangles) */
 int gg_trsv_kernel(gg_solver *s, int which, char *name, int cap);
 /* the one-launch orthogonalization kernel of the last solve's inner
- * iterations (k_arnoldi_persist<J> / k_arnoldi_wide), "" when the per-step
+ * iterations (k_arnoldi_persist<J, XG, PF>, the instantiation launched, /
+ * k_arnoldi_wide), "" when the per-step
  * kernels ran (before the first solve, or after a GG_SOLVE_CG or
  * GG_SOLVE_BICGSTAB solve, which orthogonalize nothing); returns its length */
 int gg_mgs_kernel(gg_solver *s, char *name, int cap);
+/* the k_arnoldi_persist instantiation a solve whose vectors take `units` (1, 2,
+ * 4 or 8) 16-byte units per thread launches under the current GG_MGS_GATHER /
+ * GG_MGS_PREFETCH -- the name gg_mgs_kernel reports for it; needs no device */
+int gg_mgs_kernel_for(int units, char *name, int cap);
 /* the dependency chain of triangle `which` (0 = L / Ml, 1 = U / Mr): its
  * level count (the dataflow solve), or the wavefront's critical steps
  * (nx + skew (ny - 1) for a 2D band layout, nx + ny + nz - 2 for 3D) */
@@ -479,6 +484,13 @@ int gg_batch_engine(gg_solver *s);
 /* scenario rhs's residual history of the last batched solve (as
  * gg_get_history): copies min(len, cap) entries, returns len */
 long long gg_batch_history(gg_solver *s, int rhs, double *out, long long cap);
+/* the one-launch orthogonalization kernel (rocprofv3 name) the last batched
+ * GMRES solve ran, into name[cap]: k_arnoldi_persist2<J> (two scenarios per
+ * launch; an odd last scenario on k_arnoldi_persist), k_arnoldi_persist<J, XG,
+ * PF> (one launch per scenario), "" when the per-step kernels ran with every
+ * scenario in each launch, when the scenarios ran one by one (gg_mgs_kernel
+ * names theirs), after a CG batch or before the first batch; returns its length */
+int gg_batch_mgs_kernel(gg_solver *s, char *name, int cap);
 /* gg_transient_src for nrhs source scenarios at once, each its own source set,
  * all on the solver's A = G + C/h and cdiag: scenario q's sources are
  * k = src_off[q] .. src_off[q+1]-1 (node src_node[k], kind src_kind[k],
