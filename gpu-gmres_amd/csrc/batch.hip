@@ -32,24 +32,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <string>
 #include <vector>
 
-#include "gg_solver.h"
+#include "batch_common.h"
 
 namespace gg {
 
 namespace {
-
-constexpr long long kAlign = 256;
-long long align_up(long long a) { return (a + kAlign - 1) / kAlign * kAlign; }
 
 // GG_BATCH_MGS: the orthogonalization of a batched inner iteration -- 0 the
 // per-step kernels with every scenario in each launch (k_dot, k_mgs_step,
@@ -87,15 +82,15 @@ int batch_chunk()
 
 }  // namespace
 
-// Per-scenario arena (offsets in bytes, each 256-B aligned) and the host side
-// of the read-backs.
+// The work space: the arena and read-back ring (batch_common.h), scenario 0's
+// arrays in the arena, and the orthogonalization's state.
 struct BatchWs {
-    int S = 0, m = -1;
-    long long Ppad = 0, hist_cap = 0, ngL = 0, ngU = 0;
-    long long zs = 0;                    // bytes per scenario
-    DBuf<char> arena;
-    long long oV = 0, ow = 0, oww = 0, or_ = 0, orr = 0, obb = 0, ot1 = 0, oxv = 0, obv = 0, opA = 0, opB = 0,
-              oH = 0, os = 0, ocs = 0, osn = 0, oy = 0, ohist = 0, ods = 0, oLg = 0, oUg = 0, ogran = 0, oxgran = 0;
+    BatchArena arena;                    // its method key: the restart length m
+    ReadRing<DevState> ring;
+    DevState *ds = nullptr;
+    double *V = nullptr, *w = nullptr, *ww = nullptr, *r = nullptr, *rr = nullptr, *bb = nullptr, *t1 = nullptr,
+           *xv = nullptr, *bv = nullptr, *pA = nullptr, *pB = nullptr, *H = nullptr, *sv = nullptr, *cs = nullptr,
+           *sn = nullptr, *y = nullptr, *hist = nullptr;
     // the persistent orthogonalization (GG_BATCH_MGS 1): its all-gather granules
     // per scenario (m (m+2) G, then m (m+2) sums) and XCD slots, and the
     // solver-wide election words; persist = admitted (co-residency), cleared
@@ -103,27 +98,13 @@ struct BatchWs {
     bool persist = false;
     bool persist2 = false;               // two scenarios per persistent launch (k_arnoldi_persist2)
     long long ngran = 0, nxgran = 0;
+    unsigned long long *gran = nullptr, *xgran = nullptr;
     DBuf<unsigned long long> elect;
     unsigned long long seq = 0;
-    // read-back slots: the scenarios' control blocks + the error word, written
-    // by k_pack_states_b straight into mapped pinned memory
-    static constexpr int kSlots = 4;
-    DevState *h_st[kSlots] = {};
-    DevState *d_st[kSlots] = {};
-    hipEvent_t ev[kSlots] = {};
-    std::vector<long long> hist_len;     // per scenario, of the last batched solve
     // the orthogonalization the last batched solve ran to its end with
     // (gg_batch_mgs_kernel): 2 k_arnoldi_persist2 (an odd last scenario on
     // k_arnoldi_persist), 1 k_arnoldi_persist per scenario, 0 the per-step kernels
     int ran_mgs = -1;
-    double *dp(long long off) { return reinterpret_cast<double *>(arena.p + off); }
-    ~BatchWs()
-    {
-        for (int k = 0; k < kSlots; k++) {
-            if (h_st[k]) (void)hipHostFree(h_st[k]);
-            if (ev[k]) (void)hipEventDestroy(ev[k]);
-        }
-    }
 };
 
 void batch_release(gg_solver *s)
@@ -159,46 +140,33 @@ bool batchable(const gg_solver *s)
 
 void ensure_batch(gg_solver *s, int S, int m, long long hist_need)
 {
-    BatchWs *B = s->batch;
-    if (B && B->S == S && B->m == m && B->Ppad == s->Ppad && B->hist_cap >= hist_need &&
-        B->ngL == trsv_b_granules(s->L) && B->ngU == trsv_b_granules(s->U))
-        return;
+    if (s->batch && s->batch->arena.fits(s, S, hist_need, m)) return;
     batch_release(s);
-    B = new BatchWs;
+    BatchWs *B = new BatchWs;
     s->batch = B;
-    B->S = S;
-    B->m = m;
-    B->Ppad = s->Ppad;
-    B->hist_cap = std::max<long long>(hist_need, 64);
-    B->ngL = trsv_b_granules(s->L);
-    B->ngU = trsv_b_granules(s->U);
+    BatchArena &A = B->arena;
+    A.begin(s, S, hist_need, m);
     const long long P = s->Ppad;
-    long long o = 0;
-    auto take = [&](long long bytes) {
-        const long long at = o;
-        o = align_up(o + bytes);
-        return at;
-    };
-    B->oV = take((long long)(m + 1) * P * 8);
-    B->ow = take(P * 8);
-    B->oww = take(P * 8);
-    B->or_ = take(P * 8);
-    B->orr = take(P * 8);
-    B->obb = take(P * 8);
-    B->ot1 = take(P * 8);
-    B->oxv = take(P * 8);
-    B->obv = take(P * 8);
-    B->opA = take(1024 * 8);
-    B->opB = take(1024 * 8);
-    B->oH = take((long long)(m + 1) * m * 8);
-    B->os = take((long long)(m + 1) * 8);
-    B->ocs = take((long long)(m + 1) * 8);
-    B->osn = take((long long)(m + 1) * 8);
-    B->oy = take((long long)(m + 1) * 8);
-    B->ohist = take(B->hist_cap * 8);
-    B->ods = take((long long)sizeof(DevState));
-    B->oLg = take(B->ngL * 8);
-    B->oUg = take(B->ngU * 8);
+    A.take(B->V, (long long)(m + 1) * P);
+    A.take(B->w, P);
+    A.take(B->ww, P);
+    A.take(B->r, P);
+    A.take(B->rr, P);
+    A.take(B->bb, P);
+    A.take(B->t1, P);
+    A.take(B->xv, P);
+    A.take(B->bv, P);
+    A.take(B->pA, 1024);
+    A.take(B->pB, 1024);
+    A.take(B->H, (long long)(m + 1) * m);
+    A.take(B->sv, m + 1);
+    A.take(B->cs, m + 1);
+    A.take(B->sn, m + 1);
+    A.take(B->y, m + 1);
+    A.take(B->hist, A.hist_cap);
+    A.take(B->ds, 1);
+    A.take(A.Lg, A.ngL);
+    A.take(A.Ug, A.ngU);
     {
         const int pj = arnoldi_persist_units(s->G, s->Ppad);
         const int xr = pj ? arnoldi_persist_extra(pj) : 0;
@@ -208,47 +176,17 @@ void ensure_batch(gg_solver *s, int S, int m, long long hist_need)
         if (B->persist) {
             B->ngran = (long long)m * (m + 2) * (s->G + 1);
             B->nxgran = (long long)m * (m + 2) * kMgsXcdWords;
-            B->ogran = take(B->ngran * 8);
-            B->oxgran = take(B->nxgran * 8);
+            A.take(B->gran, B->ngran);
+            A.take(B->xgran, B->nxgran);
             B->elect.alloc(kMgsElectWords);
             GG_HIP(hipMemsetAsync(B->elect.p, 0, kMgsElectWords * sizeof(unsigned long long), s->st));
         }
     }
-    B->zs = align_up(o);
-    B->arena.alloc((size_t)B->zs * S);
-    // every vector +0 in its padding slots, every dummy granule 0 (read as ready)
-    GG_HIP(hipMemsetAsync(B->arena.p, 0, (size_t)B->zs * S, s->st));
-    for (int k = 0; k < BatchWs::kSlots; k++) {
-        GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&B->h_st[k]), sizeof(DevState) * (S + 1), hipHostMallocMapped));
-        GG_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&B->d_st[k]), B->h_st[k], 0));
-        GG_HIP(hipEventCreateWithFlags(&B->ev[k], hipEventDisableTiming));
-    }
-    B->hist_len.assign(S, 0);
+    A.commit(s->st);
+    B->ring.alloc(S);
 }
 
-// the scenarios' control blocks (and the error word, in slot S's err) into
-// read-back slot k, then its event
-void readback(gg_solver *s, BatchWs *B, int k)
-{
-    launch_pack_states_b(reinterpret_cast<DevState *>(B->arena.p + B->ods), B->zs, B->S, B->d_st[k], s->err.p,
-                         s->st);
-    GG_HIP(hipEventRecord(B->ev[k], s->st));
-}
-
-struct BatchErr {
-    int bits;
-};
 struct BatchAbort {};     // a persistent orthogonalization grid was not co-resident
-// wait for slot k; the error word: bit 0 time-out (fatal), bit 1 a WD_RCP range
-// miss (the caller repeats the solve with IEEE division)
-const DevState *wait_slot(BatchWs *B, int k)
-{
-    GG_HIP(hipEventSynchronize(B->ev[k]));
-    const int err = B->h_st[k][B->S].err;
-    GG_REQUIRE((err & 1) == 0, GG_ETIMEOUT, "batched solve: wavefront boundary wait timed out");
-    if (err & 2) throw BatchErr{err};
-    return B->h_st[k];
-}
 
 struct Ctx {
     gg_solver *s;
@@ -256,36 +194,20 @@ struct Ctx {
     int S, m, G;
     long long P, zs;
     UnitMap um;
-    DevState *ds;
-    double *V, *w, *ww, *r, *rr, *bb, *t1, *xv, *bv, *pA, *pB, *H, *sv, *cs, *sn, *y, *hist;
-    unsigned long long *Lg, *Ug, *gran, *xgran;
 };
-// scenario q's copy of a per-scenario pointer
-template <class T>
-T *zq(T *p, long long zs, int q)
-{
-    return reinterpret_cast<T *>(reinterpret_cast<char *>(const_cast<typename std::remove_const<T>::type *>(p)) +
-                                 (long long)q * zs);
-}
-
-void trsv_pair(const Ctx &c, Gate g, const double *in, double *out)
-{
-    gg_solver *s = c.s;
-    launch_trsv_b(g, s->L, in, c.t1, c.Lg, s->err.p, c.S, c.zs, s->st);
-    launch_trsv_b(g, s->U, c.t1, out, c.Ug, s->err.p, c.S, c.zs, s->st);
-}
 
 void enqueue_init_b(const Ctx &c)
 {
     gg_solver *s = c.s;
+    const BatchWs &a = *c.B;
     Gate none;
-    trsv_pair(c, none, c.bv, c.bb);                                             // bb = M b
-    launch_dot_b(none, c.bb, c.bb, c.pA, c.G, c.P, c.S, c.zs, s->st);
-    launch_set_normb_b(c.pA, c.G, c.ds, c.S, c.zs, s->st);
-    launch_spmv_b(none, s->dA, c.xv, c.bv, c.rr, true, c.S, c.zs, s->st);        // rr = b - A x
-    trsv_pair(c, none, c.rr, c.r);                                              // r = M rr
-    launch_dot_b(none, c.r, c.r, c.pA, c.G, c.P, c.S, c.zs, s->st);
-    launch_init_beta_b(c.pA, c.G, c.ds, c.hist, c.S, c.zs, s->st);
+    batch_minv(s, a.arena, none, a.bv, a.t1, a.bb);                                 // bb = M b
+    launch_dot_b(none, a.bb, a.bb, a.pA, c.G, c.P, c.S, c.zs, s->st);
+    launch_set_normb_b(a.pA, c.G, a.ds, c.S, c.zs, s->st);
+    launch_spmv_b(none, s->dA, a.xv, a.bv, a.rr, true, c.S, c.zs, s->st);        // rr = b - A x
+    batch_minv(s, a.arena, none, a.rr, a.t1, a.r);                                  // r = M rr
+    launch_dot_b(none, a.r, a.r, a.pA, c.G, c.P, c.S, c.zs, s->st);
+    launch_init_beta_b(a.pA, c.G, a.ds, a.hist, c.S, c.zs, s->st);
 }
 
 // inner iterations [i0, i1) of the cycle (src/gmres.cu:566-717's loop body:
@@ -293,15 +215,16 @@ void enqueue_init_b(const Ctx &c)
 void enqueue_iters_b(const Ctx &c, int i0, int i1)
 {
     gg_solver *s = c.s;
+    const BatchWs &a = *c.B;
     for (int i = i0; i < i1; i++) {
         Gate gi;
-        gi.done = &c.ds->done;
+        gi.done = &a.ds->done;
         gi.mask = ~0;
-        gi.nit = &c.ds->nit;
+        gi.nit = &a.ds->nit;
         gi.i = i;
-        const double *vi = c.V + (long long)i * c.P;
-        launch_spmv_b(gi, s->dA, vi, nullptr, c.ww, false, c.S, c.zs, s->st);   // ww = A v_i
-        trsv_pair(c, gi, c.ww, c.w);                                            // w = M^-1 ww
+        const double *vi = a.V + (long long)i * c.P;
+        launch_spmv_b(gi, s->dA, vi, nullptr, a.ww, false, c.S, c.zs, s->st);   // ww = A v_i
+        batch_minv(s, a.arena, gi, a.ww, a.t1, a.w);                                // w = M^-1 ww
         if (c.B->persist) {
             // the persistent kernel: two scenarios per launch (k_arnoldi_persist2),
             // or one (k_arnoldi_persist) -- the same tree, the same bits
@@ -309,36 +232,36 @@ void enqueue_iters_b(const Ctx &c, int i0, int i1)
                 Gate gq = gi;
                 gq.done = zq(gi.done, c.zs, q);
                 gq.nit = zq(gi.nit, c.zs, q);
-                unsigned long long *gr = zq(c.gran, c.zs, q);
+                unsigned long long *gr = zq(a.gran, c.zs, q);
                 if (c.B->persist2 && q + 1 < c.S) {
-                    launch_arnoldi_persist2(gq, c.zs, i, c.m, zq(c.ds, c.zs, q), zq(c.w, c.zs, q), zq(c.V, c.zs, q), c.P,
-                                            zq(c.H, c.zs, q), zq(c.cs, c.zs, q), zq(c.sn, c.zs, q),
-                                            zq(c.sv, c.zs, q), zq(c.hist, c.zs, q),
+                    launch_arnoldi_persist2(gq, c.zs, i, c.m, zq(a.ds, c.zs, q), zq(a.w, c.zs, q), zq(a.V, c.zs, q), c.P,
+                                            zq(a.H, c.zs, q), zq(a.cs, c.zs, q), zq(a.sn, c.zs, q),
+                                            zq(a.sv, c.zs, q), zq(a.hist, c.zs, q),
                                             gr + (size_t)i * (c.m + 2) * c.G, c.G, c.P, s->err.p,
-                                            zq(c.xgran, c.zs, q) + (size_t)i * (c.m + 2) * kMgsXcdWords,
+                                            zq(a.xgran, c.zs, q) + (size_t)i * (c.m + 2) * kMgsXcdWords,
                                             c.B->elect.p, ++c.B->seq, c.um, s->st);
                     q++;
                     continue;
                 }
-                launch_arnoldi_persist(gq, i, c.m, zq(c.ds, c.zs, q), zq(c.w, c.zs, q), zq(c.V, c.zs, q), c.P,
-                                       zq(c.H, c.zs, q), zq(c.cs, c.zs, q), zq(c.sn, c.zs, q), zq(c.sv, c.zs, q),
-                                       zq(c.hist, c.zs, q), gr + (size_t)i * (c.m + 2) * c.G,
+                launch_arnoldi_persist(gq, i, c.m, zq(a.ds, c.zs, q), zq(a.w, c.zs, q), zq(a.V, c.zs, q), c.P,
+                                       zq(a.H, c.zs, q), zq(a.cs, c.zs, q), zq(a.sn, c.zs, q), zq(a.sv, c.zs, q),
+                                       zq(a.hist, c.zs, q), gr + (size_t)i * (c.m + 2) * c.G,
                                        gr + (size_t)c.m * (c.m + 2) * c.G + (size_t)i * (c.m + 2), c.G, c.P,
-                                       s->err.p, zq(c.xgran, c.zs, q) + (size_t)i * (c.m + 2) * kMgsXcdWords,
+                                       s->err.p, zq(a.xgran, c.zs, q) + (size_t)i * (c.m + 2) * kMgsXcdWords,
                                        c.B->elect.p, ++c.B->seq, c.um, s->st);
             }
             continue;
         }
-        double *pin = c.pA, *pout = c.pB;
-        launch_dot_b(gi, c.w, c.V, pin, c.G, c.P, c.S, c.zs, s->st);            // <w, v_0>
+        double *pin = a.pA, *pout = a.pB;
+        launch_dot_b(gi, a.w, a.V, pin, c.G, c.P, c.S, c.zs, s->st);            // <w, v_0>
         for (int k = 0; k <= i; k++) {
-            const double *vk = c.V + (long long)k * c.P;
-            const double *vn = (k < i) ? c.V + (long long)(k + 1) * c.P : c.w;
-            launch_mgs_step_b(gi, i, k, c.m, c.w, vk, vn, pin, pout, c.H, c.G, c.P, c.S, c.zs, s->st);
+            const double *vk = a.V + (long long)k * c.P;
+            const double *vn = (k < i) ? a.V + (long long)(k + 1) * c.P : a.w;
+            launch_mgs_step_b(gi, i, k, c.m, a.w, vk, vn, pin, pout, a.H, c.G, c.P, c.S, c.zs, s->st);
             std::swap(pin, pout);
         }
-        launch_arnoldi_finalize_b(gi, i, c.m, c.ds, pin, c.G, c.w, c.V + (long long)(i + 1) * c.P, c.H, c.cs, c.sn,
-                                  c.sv, c.hist, c.P, c.S, c.zs, s->st);
+        launch_arnoldi_finalize_b(gi, i, c.m, a.ds, pin, c.G, a.w, a.V + (long long)(i + 1) * c.P, a.H, a.cs, a.sn,
+                                  a.sv, a.hist, c.P, c.S, c.zs, s->st);
     }
 }
 
@@ -346,17 +269,18 @@ void enqueue_iters_b(const Ctx &c, int i0, int i1)
 void enqueue_tail_b(const Ctx &c)
 {
     gg_solver *s = c.s;
+    const BatchWs &a = *c.B;
     Gate gu;
-    gu.done = &c.ds->done;
+    gu.done = &a.ds->done;
     gu.mask = DONE_RESTART | DONE_INIT | DONE_ABORT | DONE_FINAL | DONE_EXH;
-    launch_update_b(gu, c.m, c.ds, c.H, c.sv, c.y, c.V, c.P, c.xv, c.G, c.P, c.um, c.S, c.zs, s->st);
+    launch_update_b(gu, c.m, a.ds, a.H, a.sv, a.y, a.V, c.P, a.xv, c.G, c.P, c.um, c.S, c.zs, s->st);
     Gate gr;
-    gr.done = &c.ds->done;
+    gr.done = &a.ds->done;
     gr.mask = ~0;
-    launch_spmv_b(gr, s->dA, c.xv, c.bv, c.rr, true, c.S, c.zs, s->st);
-    trsv_pair(c, gr, c.rr, c.r);
-    launch_dot_b(gr, c.r, c.r, c.pA, c.G, c.P, c.S, c.zs, s->st);
-    launch_end_cycle_b(c.pA, c.G, c.ds, c.hist, c.S, c.zs, s->st);
+    launch_spmv_b(gr, s->dA, a.xv, a.bv, a.rr, true, c.S, c.zs, s->st);
+    batch_minv(s, a.arena, gr, a.rr, a.t1, a.r);
+    launch_dot_b(gr, a.r, a.r, a.pA, c.G, c.P, c.S, c.zs, s->st);
+    launch_end_cycle_b(a.pA, c.G, a.ds, a.hist, c.S, c.zs, s->st);
 }
 
 int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, double *d_x, long long ldx,
@@ -365,65 +289,20 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
     const int m = opt->restart;
     const long long need = (long long)opt->max_iter + opt->max_iter / m + 4;
     ensure_batch(s, S, m, need);
-    BatchWs *B = s->batch;
-    B->ran_mgs = -1;
-    if (!s->err.p) s->err.alloc(1);
-    Ctx c;
-    c.s = s;
-    c.B = B;
-    c.S = S;
-    c.m = m;
-    c.G = s->G;
-    c.P = s->Ppad;
-    c.zs = B->zs;
-    c.um = solver_unit_map(s);
-    c.ds = reinterpret_cast<DevState *>(B->arena.p + B->ods);
-    c.V = B->dp(B->oV);
-    c.w = B->dp(B->ow);
-    c.ww = B->dp(B->oww);
-    c.r = B->dp(B->or_);
-    c.rr = B->dp(B->orr);
-    c.bb = B->dp(B->obb);
-    c.t1 = B->dp(B->ot1);
-    c.xv = B->dp(B->oxv);
-    c.bv = B->dp(B->obv);
-    c.pA = B->dp(B->opA);
-    c.pB = B->dp(B->opB);
-    c.H = B->dp(B->oH);
-    c.sv = B->dp(B->os);
-    c.cs = B->dp(B->ocs);
-    c.sn = B->dp(B->osn);
-    c.y = B->dp(B->oy);
-    c.hist = B->dp(B->ohist);
-    c.Lg = reinterpret_cast<unsigned long long *>(B->arena.p + B->oLg);
-    c.Ug = reinterpret_cast<unsigned long long *>(B->arena.p + B->oUg);
-    c.gran = B->persist ? reinterpret_cast<unsigned long long *>(B->arena.p + B->ogran) : nullptr;
-    c.xgran = B->persist ? reinterpret_cast<unsigned long long *>(B->arena.p + B->oxgran) : nullptr;
+    BatchWs &a = *s->batch;
+    a.ran_mgs = -1;
+    const Ctx c{s, &a, S, m, s->G, s->Ppad, a.arena.zs, solver_unit_map(s)};
     hipStream_t st = s->st;
-
-    // inputs into the solver's vector space; hand-off granules armed; control blocks
-    launch_gather_b(d_b, ldb * 8, s->lay2nat.p, c.bv, c.zs, c.P, S, st);
-    launch_gather_b(d_x, ldx * 8, s->lay2nat.p, c.xv, c.zs, c.P, S, st);
-    launch_fill_u64_b(c.Lg, s->L.wl.ngran(), kSentinel, S, c.zs, st);
-    launch_fill_u64_b(c.Ug, s->U.wl.ngran(), kSentinel, S, c.zs, st);
-    launch_init_state_b(c.ds, c.zs, S, opt->tol, opt->max_iter, m, st);
-    GG_HIP(hipMemsetAsync(s->err.p, 0, sizeof(int), st));
-    GG_HIP(hipEventRecord(s->ev0, st));
+    stage_in(s, a.arena, d_b, ldb, d_x, ldx, a.bv, a.xv,
+             [&] { launch_init_state_b(a.ds, c.zs, S, opt->tol, opt->max_iter, m, st); });
+    a.ring.begin(s, a.arena, a.ds, "batched solve: wavefront boundary wait timed out");
     enqueue_init_b(c);
 
     std::vector<Track> tr(S);
     const int K = batch_chunk();
-    int slot = 0;
-    auto next_slot = [&]() {
-        const int k = slot;
-        slot = (slot + 1) % BatchWs::kSlots;
-        return k;
-    };
     if (opt->max_iter < 1) {
         // no cycle: converged at the start or max_iter exhausted (j = 1 > max_iter)
-        const int k = next_slot();
-        readback(s, B, k);
-        const DevState *h = wait_slot(B, k);
+        const DevState *h = a.ring.post_and_wait();
         for (int q = 0; q < S; q++) {
             tr[q].fin = true;
             tr[q].relres = h[q].resid;
@@ -435,29 +314,25 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
     for (const Track &t : tr) left += !t.fin;
     while (left > 0) {
         // ---- one restart cycle, in chunks of K inner iterations
-        launch_init_cycle_b(c.ds, c.r, c.V, c.sv, c.G, c.P, S, c.zs, st);
-        if (B->persist) {
-            launch_fill_u64_b(c.gran, B->ngran, kSentinel, S, c.zs, st);
-            launch_fill_u64_b(c.xgran, B->nxgran, kSentinel, S, c.zs, st);
+        launch_init_cycle_b(a.ds, a.r, a.V, a.sv, c.G, c.P, S, c.zs, st);
+        if (a.persist) {
+            launch_fill_u64_b(a.gran, a.ngran, kSentinel, S, c.zs, st);
+            launch_fill_u64_b(a.xgran, a.nxgran, kSentinel, S, c.zs, st);
         }
         for (Track &t : tr) t.cyc_over = t.fin;
-        std::deque<std::pair<int, int>> pend;              // (read-back slot, iterations enqueued)
         int issued = 0;
         auto chunk = [&]() {
             const int i1 = std::min(issued + K, m);
             enqueue_iters_b(c, issued, i1);
             issued = i1;
-            const int k = next_slot();
-            readback(s, B, k);
-            pend.emplace_back(k, issued);
+            a.ring.post(issued);                            // tagged with the iterations enqueued
         };
         chunk();
         if (issued < m) chunk();
         const DevState *h = nullptr;
         while (true) {
-            const auto [k, iend] = pend.front();
-            pend.pop_front();
-            h = wait_slot(B, k);
+            int iend = 0;
+            h = a.ring.wait_oldest(&iend);
             for (int q = 0; q < S; q++)
                 if (h[q].done & DONE_ABORT) throw BatchAbort{};
             bool over = true;
@@ -470,7 +345,7 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
             }
             if (over) break;
             if (issued < m) chunk();
-            GG_REQUIRE(!pend.empty(), GG_EHIP, "batched solve: cycle did not end after m iterations");
+            GG_REQUIRE(a.ring.pending(), GG_EHIP, "batched solve: cycle did not end after m iterations");
         }
         // the scenarios' outcomes as far as the last read-back decides them
         std::vector<DevState> hs(h, h + S);
@@ -499,9 +374,7 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
             }
         }
         if (need_tail) {
-            const int k = next_slot();
-            readback(s, B, k);
-            const DevState *ht = wait_slot(B, k);
+            const DevState *ht = a.ring.post_and_wait();
             for (int q = 0; q < S; q++) {
                 Track &t = tr[q];
                 if (t.fin) continue;
@@ -526,20 +399,12 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
         left = 0;
         for (const Track &t : tr) left += !t.fin;
     }
-    GG_HIP(hipEventRecord(s->ev1, st));
-    launch_gather_b(c.xv, c.zs, s->nat2lay.p, d_x, ldx * 8, s->A.n, S, st);
-    {
-        const int k = next_slot();
-        readback(s, B, k);                      // the error word after every launch
-        (void)wait_slot(B, k);
-    }
-    float ms = 0.f;
-    GG_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    const float ms = stage_out(s, a.arena, a.ring, a.xv, d_x, ldx);
     int rc = GG_OK;
-    B->ran_mgs = B->persist2 ? 2 : B->persist ? 1 : 0;
+    a.ran_mgs = a.persist2 ? 2 : a.persist ? 1 : 0;
     for (int q = 0; q < S; q++) {
         const Track &t = tr[q];
-        B->hist_len[q] = t.hist_len;
+        a.arena.hist_len[q] = t.hist_len;
         if (t.ret) rc = 1;
         if (res) {
             res[q].status = t.ret;
@@ -559,7 +424,7 @@ int solve_batch_seq(gg_solver *s, int S, const double *d_b, long long ldb, doubl
                     const gg_options *opt, gg_result *res)
 {
     int rc = GG_OK;
-    if (s->batch) s->batch->hist_len.assign(S, 0);
+    if (s->batch) s->batch->arena.hist_len.assign(S, 0);
     if (s->batch) s->batch->ran_mgs = -1;
     for (int q = 0; q < S; q++) {
         gg_result r{};
@@ -597,13 +462,12 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
             if (attempt >= 2) throw Error{GG_EHIP, "gg_solve_batch: fallbacks exhausted"};
             s->batch->persist = false;
             s->batch->persist2 = false;
-        } catch (BatchErr &e) {
+        } catch (Fallback &f) {
             // a WD_RCP range miss: IEEE division for the solver's life, repeat
             // (d_x is written only at the end)
             GG_HIP(hipStreamSynchronize(s->st));
             if (attempt >= 2) throw Error{GG_EHIP, "gg_solve_batch: fallbacks exhausted"};
-            for (DevTri *T : {&s->L, &s->U})
-                if (T->kind == DevTri::WAVE2D && T->div == WD_RCP) T->div = WD_HW;
+            apply_fallback(s, f);
         }
     }
 }
@@ -622,33 +486,13 @@ std::string batch_mgs_kernel(gg_solver *s)
 long long batch_history(gg_solver *s, int q, double *out, long long cap)
 {
     if (s->batch_last_cg) return cg_batch_history(s, q, out, cap);
-    BatchWs *B = s->batch;
-    GG_REQUIRE(B && q >= 0 && q < B->S && B->hist_len[q] > 0, GG_ESTATE,
-               "gg_batch_history: no batched solve holds that scenario");
-    const long long n = B->hist_len[q];
-    if (out && cap > 0)
-        GG_HIP(hipMemcpy(out, B->arena.p + (long long)q * B->zs + B->ohist, std::min(n, cap) * sizeof(double),
-                         hipMemcpyDeviceToHost));
-    return n;
+    GG_REQUIRE(s->batch, GG_ESTATE, "gg_batch_history: no batched solve holds that scenario");
+    return s->batch->arena.history(s->batch->hist, q, out, cap);
 }
 
 }  // namespace gg
 
 // ======================================================================= C ABI
-namespace {
-int fail_b(const gg::Error &e)
-{
-    gg::set_error(e.msg);
-    return e.code;
-}
-}  // namespace
-#define GG_BAPI_BEGIN try {
-#define GG_BAPI_END                                                                 \
-    }                                                                               \
-    catch (const gg::Error &e) { return fail_b(e); }                                \
-    catch (const std::bad_alloc &) { return fail_b({GG_ENOMEM, "host allocation failed"}); } \
-    catch (const std::exception &e) { return fail_b({GG_EINVAL, e.what()}); }
-
 using namespace gg;
 
 extern "C" {
@@ -656,61 +500,45 @@ extern "C" {
 int gg_solve_batch_device(gg_solver *s, int nrhs, const double *d_b, long long ldb, double *d_x, long long ldx,
                           const gg_options *opt, gg_result *res)
 {
-    GG_BAPI_BEGIN
+    GG_API_BEGIN
     GG_REQUIRE(s && d_b && d_x, GG_EINVAL, "null argument");
     return solve_batch(s, nrhs, d_b, ldb, d_x, ldx, opt, res);
-    GG_BAPI_END
+    GG_API_END
 }
 
 int gg_solve_batch(gg_solver *s, int nrhs, const double *b, long long ldb, double *x, long long ldx,
                    const gg_options *opt, gg_result *res)
 {
-    GG_BAPI_BEGIN
-    GG_REQUIRE(s && b && x, GG_EINVAL, "null argument");
-    GG_REQUIRE(s->have_A, GG_ESTATE, "gg_solve_batch: no matrix");
-    GG_REQUIRE(nrhs >= 1 && ldb >= s->A.n && ldx >= s->A.n, GG_EINVAL, "gg_solve_batch: bad nrhs / leading dimension");
-    GG_HIP(hipSetDevice(s->device));
-    const int n = s->A.n;
-    DBuf<double> db, dx;
-    db.alloc((size_t)nrhs * n);
-    dx.alloc((size_t)nrhs * n);
-    for (int q = 0; q < nrhs; q++) {
-        GG_HIP(hipMemcpyAsync(db.p + (size_t)q * n, b + (size_t)q * ldb, n * sizeof(double), hipMemcpyHostToDevice, s->st));
-        GG_HIP(hipMemcpyAsync(dx.p + (size_t)q * n, x + (size_t)q * ldx, n * sizeof(double), hipMemcpyHostToDevice, s->st));
-    }
-    const int rc = solve_batch(s, nrhs, db.p, n, dx.p, n, opt, res);
-    for (int q = 0; q < nrhs; q++)
-        GG_HIP(hipMemcpyAsync(x + (size_t)q * ldx, dx.p + (size_t)q * n, n * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    GG_HIP(hipStreamSynchronize(s->st));
-    return rc;
-    GG_BAPI_END
+    GG_API_BEGIN
+    return solve_batch_host(s, solve_batch, "gg_solve_batch", true, nrhs, b, ldb, x, ldx, opt, res);
+    GG_API_END
 }
 
 long long gg_batch_history(gg_solver *s, int rhs, double *out, long long cap)
 {
-    GG_BAPI_BEGIN
+    GG_API_BEGIN
     GG_REQUIRE(s, GG_EINVAL, "null solver");
     return batch_history(s, rhs, out, cap);
-    GG_BAPI_END
+    GG_API_END
 }
 
 int gg_batch_engine(gg_solver *s)
 {
-    GG_BAPI_BEGIN
+    GG_API_BEGIN
     GG_REQUIRE(s, GG_EINVAL, "null solver");
     GG_REQUIRE(s->pkind >= 0, GG_ESTATE, "gg_batch_engine: no preconditioner");
     return batch_engine_on(s) ? 1 : 0;
-    GG_BAPI_END
+    GG_API_END
 }
 
 int gg_batch_mgs_kernel(gg_solver *s, char *name, int cap)
 {
-    GG_BAPI_BEGIN
+    GG_API_BEGIN
     GG_REQUIRE(s && name && cap > 0, GG_EINVAL, "null argument");
     const std::string k = batch_mgs_kernel(s);
     std::snprintf(name, (size_t)cap, "%s", k.c_str());
     return (int)k.size();
-    GG_BAPI_END
+    GG_API_END
 }
 
 int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const double *cdiag, const int *src_off,
@@ -718,10 +546,10 @@ int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const doubl
                        int nport, const int *port, double *x, const gg_options *opt, double *port_out,
                        int *iters_total)
 {
-    GG_BAPI_BEGIN
+    GG_API_BEGIN
     return transient_batch(s, false, nrhs, nsteps, h, cdiag, src_off, src_node, src_kind, src_ptr, src_data, nport,
                            port, x, opt, port_out, iters_total);
-    GG_BAPI_END
+    GG_API_END
 }
 
 }  // extern "C"

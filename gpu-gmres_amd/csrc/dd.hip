@@ -26,6 +26,7 @@
 #include <functional>
 #include <memory>
 
+#include "gg_api.h"
 #include "ggmres_dd.h"
 #include "kernels.h"
 
@@ -130,18 +131,6 @@ struct gg_dd {
 };
 
 namespace {
-
-int fail(const Error &e)
-{
-    set_error(e.msg);
-    return e.code;
-}
-#define GG_API_BEGIN try {
-#define GG_API_END                                                                          \
-    }                                                                                       \
-    catch (const gg::Error &e) { return fail(e); }                                          \
-    catch (const std::bad_alloc &) { return fail({GG_ENOMEM, "host allocation failed"}); } \
-    catch (const std::exception &e) { return fail({GG_EINVAL, e.what()}); }
 
 void set_dev(gg_dd *d) { GG_HIP(hipSetDevice(d->device)); }
 

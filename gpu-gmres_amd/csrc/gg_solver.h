@@ -1,5 +1,9 @@
 // gg_solver.h -- the single-device solver object behind the C ABI (solver.hip)
-// and the many-RHS batch driver (batch.hip).
+// and what its engines in other files declare to each other: the many-RHS
+// batches (batch.hip: GMRES, cg_batch.hip: CG; the arena, read-back ring and
+// staging they share are batch_common.h's), the short-recurrence solves (cg.hip,
+// bicgstab.hip) and the read-back pipe, error-word triage and fallback they all
+// use.  The C ABI's exception boundary is gg_api.h.
 #pragma once
 
 #include <algorithm>
@@ -51,6 +55,9 @@ struct Fallback {
 // Returns when none of kErrSolve is set.
 constexpr int kErrSolve = 8 | 1 | 2;
 void raise_err(int err);
+// for the rest of the solver's life: every WD_RCP triangle divides (bit 1),
+// every 3D tile triangle claims its tiles from the queue (bit 3)
+void apply_fallback(gg_solver *s, const Fallback &f);
 // The read-back pipe (solver.hip): a solve enqueues work one unit (a restart
 // cycle, a chunk of iterations) ahead of the state the host has read.  Each
 // unit ends in a post: the control block and the error word copied into one of

@@ -19,8 +19,7 @@ struct DevState {
     int hist_len;   // history entries recorded before this cycle
     int m;
     int upd_k;      // column count - 1 used by the last Update
-    int err;        // device-side error (1 = wavefront wait timed out)
-    int pad;
+    int pad[2];
 };
 constexpr int DONE_INNER = 1, DONE_RESTART = 2, DONE_INIT = 4, DONE_ABORT = 8;
 // a cycle enqueued behind the one that ends the solve (the host's pipelined
@@ -404,8 +403,9 @@ void launch_fill_u64_b(unsigned long long *p, long long n, unsigned long long v,
 void launch_gather_b(const double *in, long long zin, const long long *idx, double *out, long long zout,
                      long long n, int nsc, hipStream_t st);
 void launch_init_state_b(DevState *ds, long long zs, int nsc, double tol, int max_iter, int m, hipStream_t st);
-// out[q] = scenario q's control block, q < nsc; out[nsc].err = *err
-void launch_pack_states_b(const DevState *ds, long long zs, int nsc, DevState *out, const int *err, hipStream_t st);
+// out[q] = scenario q's control block (DevState or CgState), q < nsc; the int at out + nsc = *err
+template <class State>
+void launch_pack_states_b(const State *st0, long long zs, int nsc, State *out, const int *err, hipStream_t st);
 // u = each scenario's sources at time index it (soff: nsc + 1 offsets into the
 // concatenated kind / dptr tables, maxsrc the largest count); w_q = B_q u + (C/h) x_q
 // with scenario q's B^T rows at sptr + q * (n + 1) (sidx: global source indices)
@@ -443,9 +443,6 @@ void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, i
 // and launch_cg_* on a grid (G, nsc), the control block, history and partials
 // per scenario like the vectors; the gate's done / nit = scenario 0's words
 void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st);
-// out[q] = scenario q's control block, q < nsc; *err_out = *err
-void launch_pack_cg_states_b(const CgState *cs, long long zs, int nsc, CgState *out, const int *err, int *err_out,
-                             hipStream_t st);
 void launch_normb_b(const double *part, int G, double *normb, int nsc, long long zs, hipStream_t st);
 void launch_cg_pq_b(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, int nsc,
                     long long zs, hipStream_t st);

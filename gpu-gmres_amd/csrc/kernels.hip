@@ -3291,16 +3291,18 @@ __global__ void k_init_state_b(DevState *ds, long long zs, int nsc, double tol, 
     h.j = 1;
     *zp(ds, zs, q) = h;
 }
-// the scenarios' control blocks side by side (one copy to the host per cycle)
-__global__ void k_pack_states_b(const DevState *ds, long long zs, int nsc, DevState *out, const int *err)
+// the scenarios' control blocks (DevState, CgState) side by side in a read-back
+// slot, and behind them the error word after every launch before this one
+// (batch_common.h ReadRing: one copy to the host per chunk)
+template <class State>
+__global__ void k_pack_states_b(const State *st0, long long zs, int nsc, State *out, const int *err)
 {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nsc) out[q] = *zp(ds, zs, q);
-    if (q == nsc) out[nsc].err = *err;          // the error word after every launch before this one
+    if (q < nsc) out[q] = *zp(st0, zs, q);
+    if (q == nsc) *reinterpret_cast<int *>(out + nsc) = *err;
 }
-// the same for the CG batch's control blocks (cg_batch.hip): every scenario's
-// CgState at the start of a solve; all of them and the error word (*err_out)
-// into a read-back slot
+// the CG batch's control blocks (cg_batch.hip): every scenario's CgState at the
+// start of a solve
 __global__ void k_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter)
 {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3309,13 +3311,6 @@ __global__ void k_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol
     h.tol = tol;
     h.max_iter = max_iter;
     *zp(cs, zs, q) = h;
-}
-__global__ void k_pack_cg_states_b(const CgState *cs, long long zs, int nsc, CgState *out, const int *err,
-                                   int *err_out)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nsc) out[q] = *zp(cs, zs, q);
-    if (q == nsc) *err_out = *err;
 }
 // transient step of every scenario: u_sc = its sources at time index it; w_sc
 // = B_sc u_sc + (C/h) x_sc (k_sources + k_transient_rhs per scenario; tables
@@ -6553,10 +6548,13 @@ void launch_init_state_b(DevState *ds, long long zs, int nsc, double tol, int ma
 {
     k_init_state_b<<<(nsc + 63) / 64, 64, 0, st>>>(ds, zs, nsc, tol, max_iter, m);
 }
-void launch_pack_states_b(const DevState *ds, long long zs, int nsc, DevState *out, const int *err, hipStream_t st)
+template <class State>
+void launch_pack_states_b(const State *st0, long long zs, int nsc, State *out, const int *err, hipStream_t st)
 {
-    k_pack_states_b<<<(nsc + 64) / 64, 64, 0, st>>>(ds, zs, nsc, out, err);
+    k_pack_states_b<State><<<(nsc + 64) / 64, 64, 0, st>>>(st0, zs, nsc, out, err);
 }
+template void launch_pack_states_b<DevState>(const DevState *, long long, int, DevState *, const int *, hipStream_t);
+template void launch_pack_states_b<CgState>(const CgState *, long long, int, CgState *, const int *, hipStream_t);
 void launch_transient_step_b(int n, int nsc, int maxsrc, const int *soff, const int *kind, const int *dptr,
                              const double *data, int it, double h, double *u, const int *sptr, const int *sidx,
                              const double *cdiag, const double *x, double *w, long long ldx, hipStream_t st)
@@ -6719,11 +6717,6 @@ void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, i
 void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st)
 {
     k_init_cg_state_b<<<(nsc + 63) / 64, 64, 0, st>>>(cs, zs, nsc, tol, max_iter);
-}
-void launch_pack_cg_states_b(const CgState *cs, long long zs, int nsc, CgState *out, const int *err, int *err_out,
-                             hipStream_t st)
-{
-    k_pack_cg_states_b<<<(nsc + 64) / 64, 64, 0, st>>>(cs, zs, nsc, out, err, err_out);
 }
 void launch_normb_b(const double *part, int G, double *normb, int nsc, long long zs, hipStream_t st)
 {

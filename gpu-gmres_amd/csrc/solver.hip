@@ -21,6 +21,7 @@
 #include <memory>
 #include <numeric>
 
+#include "gg_api.h"
 #include "kernels.h"
 #include "gg_solver.h"
 
@@ -651,19 +652,6 @@ using namespace gg;
 // struct gg_solver: gg_solver.h (shared with batch.hip)
 
 namespace {
-
-int fail(const Error &e)
-{
-    set_error(e.msg);
-    return e.code;
-}
-
-#define GG_API_BEGIN try {
-#define GG_API_END                                                   \
-    }                                                                \
-    catch (const gg::Error &e) { return fail(e); }                   \
-    catch (const std::bad_alloc &) { return fail({GG_ENOMEM, "host allocation failed"}); } \
-    catch (const std::exception &e) { return fail({GG_EINVAL, e.what()}); }
 
 void check_csr(int n, const int *rp, const int *ci, const double *v, const char *what)
 {
@@ -1385,6 +1373,16 @@ void gg::pipe_release(gg_solver *s)
     }
 }
 
+// for the rest of the solver's life: every WD_RCP triangle divides (bit 1),
+// every 3D tile triangle claims its tiles from the queue (bit 3)
+void gg::apply_fallback(gg_solver *s, const Fallback &f)
+{
+    for (DevTri *T : {&s->L, &s->U}) {
+        if ((f.bits & 2) && T->kind == DevTri::WAVE2D && T->div == WD_RCP) T->div = WD_HW;
+        if ((f.bits & 8) && T->kind == DevTri::WAVE2D && T->wl.tile) T->tile_queue = true;
+    }
+}
+
 namespace {
 
 // the control block and the error word in one round trip (after a cycle), with
@@ -1394,15 +1392,6 @@ DevState read_state_checked(gg_solver *s)
     pipe_post(s, 0, s->ds.p, sizeof(DevState), false);
     raise_err(pipe_wait(s, 0));
     return pipe_state<DevState>(s, 0);
-}
-// for the rest of the solver's life: every WD_RCP triangle divides (bit 1),
-// every 3D tile triangle claims its tiles from the queue (bit 3)
-void apply_fallback(gg_solver *s, const Fallback &f)
-{
-    for (DevTri *T : {&s->L, &s->U}) {
-        if ((f.bits & 2) && T->kind == DevTri::WAVE2D && T->div == WD_RCP) T->div = WD_HW;
-        if ((f.bits & 8) && T->kind == DevTri::WAVE2D && T->wl.tile) T->tile_queue = true;
-    }
 }
 
 // A persistent orthogonalization grid that was not co-resident aborted the

@@ -220,6 +220,47 @@ def test_solve_batch_sequential_fallback(monkeypatch):
     s.close()
 
 
+def test_solve_batch_second_grid_in_the_same_arena():
+    """One solver, two grids, one arena shape: 60 x 52, then 60 x 40 on the same
+    solver.  Both are one band of at most 64 lines with lines of 60 steps, so
+     T = roundup(60 + 63, 32) = 128, P = 1 * 128 * 64 = 8192 (a
+    multiple of 512) and each triangle's batch granules 1 * 1 * T + 128 * 1 + 64 =
+    320 for both: restart, nrhs, Ppad and the granule counts all match, only the
+    matrix changed -- and slots that held rows 40 .. 51 of the first grid are
+    padding in the second.  The second grid's batch must be a fresh solver's, bit
+    for bit."""
+    grids = [(60, 52), (60, 40)]
+    kw = dict(restart=30, max_iter=3000, tol=1e-10)
+    A = [M.laplacian_5pt(*g) for g in grids]
+    B = [_rhs_set(a, 3, seed=3) for a in A]
+    f = ggmres.Solver(0)
+    f.set_matrix(A[1])
+    f.set_precond_ilu0()
+    fresh = f.solve_batch(B[1], **kw)
+    f.close()
+    s = ggmres.Solver(0)
+    lay = []
+    for a, b in zip(A, B):
+        s.set_matrix(a)
+        s.set_precond_ilu0()
+        assert s.uses_wavefront and s.batch_engine
+        lay.append(s.layout())
+        g = s.solve_batch(b, **kw)
+    s.close()
+    for (nx, ny), (l2n, G) in zip(grids, lay):
+        want, Gw = device_layout(nx * ny, nx=nx)
+        assert l2n.size == 8192 and G == Gw == lay[0][1] and np.array_equal(l2n, want)
+        assert np.count_nonzero(l2n >= 0) == nx * ny
+    assert np.any((lay[0][0] >= 0) & (lay[1][0] < 0))           # rows of the first grid where the second pads
+    assert fresh["ret"] == 0 and max(fresh["iters"]) > 10 and fresh["iters"][2] == 0
+    assert g["ret"] == fresh["ret"]
+    for k in ("status", "iters", "inner", "restarts", "relres"):
+        assert g[k] == fresh[k], k
+    for q in range(3):
+        assert np.array_equal(g["hist"][q], fresh["hist"][q]), q
+        assert np.array_equal(g["x"][q], fresh["x"][q]), q
+
+
 @pytest.mark.parametrize("case", ["ilu1_skewed", "grid3d", "nrhs1", "max_iter0"])
 def test_solve_batch_edges_match_single(case):
     """configurations at the batch's edges, each scenario against its own

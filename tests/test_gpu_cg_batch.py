@@ -302,6 +302,42 @@ def test_transient_cg_batch_bitexact_vs_single():
         s.close()
 
 
+def test_cg_batch_second_grid_in_the_same_arena():
+    """test_gpu_batch.test_solve_batch_second_grid_in_the_same_arena for CG: 60 x 52,
+    then 60 x 40 on the same solver -- the same nrhs, Ppad (8192) and granule
+    counts, rows of the first grid where the second pads.  The second grid's
+    batch is a fresh solver's, bit for bit."""
+    A = [M.laplacian_5pt(60, 52), M.laplacian_5pt(60, 40)]
+    B = [rhs_set(a, 3, seed=3) for a in A]
+    f = make(A[1])
+    try:
+        fresh = f.solve_cg_batch(B[1], max_iter=3000, tol=1e-10)
+    finally:
+        f.close()
+    s = ggmres.Solver(0)
+    try:
+        lay = []
+        for a, b in zip(A, B):
+            s.set_matrix(a)
+            s.set_precond_ilu0()
+            s.set_division(ggmres.DIV_EXACT)
+            assert s.uses_wavefront and s.batch_engine
+            lay.append(s.layout())
+            g = s.solve_cg_batch(b, max_iter=3000, tol=1e-10)
+    finally:
+        s.close()
+    assert lay[0][0].size == lay[1][0].size == 8192 and lay[0][1] == lay[1][1]
+    assert [np.count_nonzero(l >= 0) for l, _ in lay] == [60 * 52, 60 * 40]
+    assert np.any((lay[0][0] >= 0) & (lay[1][0] < 0))
+    assert fresh["ret"] == 0 and max(fresh["iters"]) > 30 and fresh["iters"][2] == 0
+    assert g["ret"] == fresh["ret"]
+    for k in ("status", "iters", "inner", "restarts", "relres"):
+        assert g[k] == fresh[k], k
+    for q in range(3):
+        assert np.array_equal(g["hist"][q], fresh["hist"][q]), q
+        assert np.array_equal(g["x"][q], fresh["x"][q]), q
+
+
 def test_cg_and_gmres_batches_alternate_on_one_solver():
     """each solve on a solver that ran the others gives a fresh solver's bits"""
     A = M.laplacian_5pt(40, 33)
