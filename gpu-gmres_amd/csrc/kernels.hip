@@ -3636,6 +3636,93 @@ __device__ __forceinline__ void gen_rot(double dx, double dy, double &cs, double
     }
 }
 
+// ---- the Givens update of Hessenberg column i, written once -------------------
+// The reference's sequence -- apply_rot(Hc[k], Hc[k+1], cs[k], sn[k]) for k < i,
+// gen_rot, the two last apply_rot, the residual test -- as a pair of steps that
+// keep the column on chip: `lo` is Hc[k] with rotations 0..k-1 applied, the one
+// entry the next rotation still needs.  The same calls on the same operands in
+// the same order as the loop over memory, so the same bits; what changes is
+// that no rotation waits for the previous one's stores and its own loads.
+//
+// givens_absorb: h_{k+1} is known -- rotation k on (Hc[k], h_{k+1}); returns the
+// final Hc[k], keeps the rotated Hc[k+1]
+__device__ __forceinline__ double givens_absorb(double &lo, double hnext, double c, double s)
+{
+    apply_rot(lo, hnext, c, s);
+    const double fin = lo;
+    lo = hnext;
+    return fin;
+}
+// what the column's last step reads besides the column: loaded up front
+struct GivensIn {
+    double si, si1, normb, tol;
+    int hist_len;
+};
+__device__ __forceinline__ GivensIn givens_load(const double *s, const DevState *ds, int i)
+{
+    GivensIn in;
+    in.si = s[i];
+    in.si1 = s[i + 1];
+    in.normb = ds->normb;
+    in.tol = ds->tol;
+    in.hist_len = ds->hist_len;
+    return in;
+}
+// givens_finish: lo = Hc[i] (rotations 0..i-1 applied), hn = ||w||: the new
+// rotation on the column and on s, the residual, the history entry and the
+// convergence flag -- arithmetic on registers, then stores
+struct GivensOut {
+    double c, s, resid;
+};
+__device__ __forceinline__ GivensOut givens_finish(double lo, double hn, const GivensIn &in, int i, double *Hc,
+                                                   double *cs, double *sn, double *s, double *hist, DevState *ds)
+{
+    double hi = lo, hi1 = hn, c, sv;
+    gen_rot(hi, hi1, c, sv);
+    apply_rot(hi, hi1, c, sv);
+    double si = in.si, si1 = in.si1;
+    apply_rot(si, si1, c, sv);
+    const double resid = fabs(si1) / in.normb;
+    Hc[i] = hi;
+    Hc[i + 1] = hi1;
+    cs[i] = c;
+    sn[i] = sv;
+    s[i] = si;
+    s[i + 1] = si1;
+    hist[in.hist_len + i] = resid;
+    ds->resid = resid;
+    if (resid < in.tol) {                // "<" (src/gmres.cu:654)
+        ds->conv_i = i;
+        ds->done = DONE_INNER;
+    }
+    return {c, sv, resid};
+}
+// the whole column from memory (the per-step kernels' finalize): Hc[0..i] hold
+// the raw h_k.  The inputs of kGivensBatch rotations are loaded together, and
+// every load of the last step goes out before the first rotation, so the chain
+// is one memory latency per batch instead of one per rotation.
+constexpr int kGivensBatch = 8;
+__device__ __forceinline__ void givens_column(int i, double hn, double *Hc, double *cs, double *sn, double *s,
+                                              double *hist, DevState *ds)
+{
+    const GivensIn in = givens_load(s, ds, i);
+    double lo = Hc[0];
+    for (int k0 = 0; k0 < i; k0 += kGivensBatch) {
+        double h[kGivensBatch], c[kGivensBatch], r[kGivensBatch];
+#pragma unroll
+        for (int q = 0; q < kGivensBatch; q++) {
+            const int k = k0 + q < i ? k0 + q : i - 1;      // (the tail repeats a valid entry, unused)
+            h[q] = Hc[k + 1];
+            c[q] = cs[k];
+            r[q] = sn[k];
+        }
+#pragma unroll
+        for (int q = 0; q < kGivensBatch; q++)
+            if (k0 + q < i) Hc[k0 + q] = givens_absorb(lo, h[q], c[q], r[q]);
+    }
+    givens_finish(lo, hn, in, i, Hc, cs, sn, s, hist, ds);
+}
+
 // H[i+1,i] = ||w||; Givens on column i; residual check; v_{i+1} = w * (1/H[i+1,i])
 __global__ __launch_bounds__(kBlock) void k_arnoldi_finalize(Gate g, int i, int m, DevState *ds,
                                                              const double *part, int G,
@@ -3658,25 +3745,7 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_finalize(Gate g, int i, int 
         hist = zp(hist, zs, sc);
     }
     const double hn = sqrt(sum_partials(part, G));
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const int ld = m + 1;
-        double *Hc = H + i * ld;
-        Hc[i + 1] = hn;
-        for (int k = 0; k < i; k++) apply_rot(Hc[k], Hc[k + 1], cs[k], sn[k]);
-        double c, sv;
-        gen_rot(Hc[i], Hc[i + 1], c, sv);
-        cs[i] = c;
-        sn[i] = sv;
-        apply_rot(Hc[i], Hc[i + 1], c, sv);
-        apply_rot(s[i], s[i + 1], c, sv);
-        const double resid = fabs(s[i + 1]) / ds->normb;
-        hist[ds->hist_len + i] = resid;
-        ds->resid = resid;
-        if (resid < ds->tol) {               // "<" (src/gmres.cu:654)
-            ds->conv_i = i;
-            ds->done = DONE_INNER;
-        }
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) givens_column(i, hn, H + i * (m + 1), cs, sn, s, hist, ds);
     // lucky breakdown (hn == 0): the reference divides by zero; v_{i+1} := 0
     const double inv = (hn != 0.0) ? 1.0 / hn : 0.0;
     const long long stride = (long long)gridDim.x * kBlock;
@@ -4046,25 +4115,7 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_finalize_x(Gate g, int i, in
     }
     __syncthreads();
     const double hn = sqrt(nrm2);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {      // as k_arnoldi_finalize
-        const int ld = m + 1;
-        double *Hc = H + i * ld;
-        Hc[i + 1] = hn;
-        for (int k = 0; k < i; k++) apply_rot(Hc[k], Hc[k + 1], cs[k], sn[k]);
-        double c, sv;
-        gen_rot(Hc[i], Hc[i + 1], c, sv);
-        cs[i] = c;
-        sn[i] = sv;
-        apply_rot(Hc[i], Hc[i + 1], c, sv);
-        apply_rot(s[i], s[i + 1], c, sv);
-        const double resid = fabs(s[i + 1]) / ds->normb;
-        hist[ds->hist_len + i] = resid;
-        ds->resid = resid;
-        if (resid < ds->tol) {
-            ds->conv_i = i;
-            ds->done = DONE_INNER;
-        }
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) givens_column(i, hn, H + i * (m + 1), cs, sn, s, hist, ds);
     const double inv = (hn != 0.0) ? 1.0 / hn : 0.0;
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long u = blockIdx.x * (long long)kBlock + threadIdx.x; u < units; u += stride) {
@@ -4415,6 +4466,7 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
     // granules per thread loaded at once in the all-gathers (persist_np; J =
     // 8 polls them one by one: the parallel form would cost it an occupancy step)
     constexpr int kNP = persist_np(J);
+    const long long t_in = trace ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
     if (gated(g)) return;
     if (block_aborted(ds)) return;                            // co-residency (gather_first)
     // XG 3: the first kXcds blocks hold no units; they only reduce (below)
@@ -4459,6 +4511,14 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
         if (trow >= 0 && threadIdx.x == 0)
             trace[((long long)trow * (i + 2) + k) * 4 + ph] = (long long)__builtin_amdgcn_s_memrealtime();
     };
+    // the launch's head and tail (row 2): 0 entry, 1 gate / abort / election
+    // resolved, 2 w and v_0 landed, 4 the Givens block done, 5 v_{i+1} stored
+    auto stamp_ht = [&](int ph, long long t = -1) {
+        if (trow == 0 && threadIdx.x == 0)
+            trace[(long long)2 * (i + 2) * 4 + ph] = t >= 0 ? t : (long long)__builtin_amdgcn_s_memrealtime();
+    };
+    stamp_ht(0, t_in);
+    stamp_ht(1);
     double2 w[J], vk[J], vn[J];
     [[maybe_unused]] double2 vl[PF == 2 ? J : 1];             // PF 2: the third basis buffer
     bool val[J];                                              // unit holds a real row (UnitMap)
@@ -4480,6 +4540,20 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
     if constexpr (PF == 2) {
         if (i >= 1) load_v(1, vn);                            // v_1, behind w and v_0
     }
+    // unit-block 0 keeps the column's first kRotLds stored rotations cs / sn in
+    // LDS (1 KB: a restart of up to 65 lies in it whole; the entries beyond it
+    // are read from memory where they are used, in a gather's shadow).  One
+    // coalesced, looped pass, in program order BEHIND the loads of w and v_0 so
+    // that its wait delays none of them; visible after publish(0)'s barrier.
+    constexpr int kRotLds = 64;
+    __shared__ double rot_c[kRotLds], rot_s[kRotLds];
+    if (ub == 0) {
+        const int nrot = i < kRotLds ? i : kRotLds;
+        for (int k = threadIdx.x; k < nrot; k += kBlock) {
+            rot_c[k] = cs[k];
+            rot_s[k] = sn[k];
+        }
+    }
     int par = 0;                                              // block_sum_pp's LDS row
     auto publish = [&](int k, double acc) {
         acc = block_sum_pp(acc, par);
@@ -4492,7 +4566,10 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
             acc += w[j].x * vk[j].x;
             acc += w[j].y * vk[j].y;
         }
+    stamp_ht(2);
     publish(0, acc);                                          // <w, v_0>
+    double *const Hc = H + i * (m + 1);                       // column i (unit-block 0's thread 0)
+    double hlo = 0.0;                                         // its entry still to be rotated
     // step k: h_k, w -= h_k v_k, the partial of the next dot (v_{k+1}, or the
     // norm), published.  cur = v_k, nxt = v_{k+1} (loaded), lnd = the buffer
     // v_{k+2} lands in (PF 2; the three rotate, no register copies -- a copy of
@@ -4523,7 +4600,6 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
             if (k + 2 <= i) load_v(k + 2, lnd);
         }
         stamp(k, 1);
-        if (ub == 0 && threadIdx.x == 0) H[k + i * (m + 1)] = h;
         const double a = -h;
         double acc = 0.0;
 #pragma unroll
@@ -4539,6 +4615,18 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
         stamp(k, 2);
         publish(k + 1, acc);
         stamp(k, 3);
+        // the column, rotated as its entries arrive (givens_absorb): h_k lets
+        // rotation k-1 go and makes Hc[k-1] final -- behind the publication,
+        // in the next gather's shadow
+        if (ub == 0 && threadIdx.x == 0) {
+            if (k == 0) {
+                hlo = h;
+            } else {
+                const int q = k - 1;
+                const double c = q < kRotLds ? rot_c[q] : cs[q], r = q < kRotLds ? rot_s[q] : sn[q];
+                Hc[q] = givens_absorb(hlo, h, c, r);
+            }
+        }
         return true;
     };
     if constexpr (PF == 2) {
@@ -4557,29 +4645,18 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
         }
     }
     stamp(i + 1, 0);
+    // what the column's last step reads (s[i], s[i+1], normb, tol, hist_len):
+    // requested here, in flight during the norm's gather
+    GivensIn gin = {};
+    if (ub == 0 && threadIdx.x == 0) gin = givens_load(s, ds, i);
     const double hn = sqrt(XG >= 2 ? gather_xcd<kNP>(gran + (long long)(i + 1) * G, xslot(i + 1), i + 1, G, red, err, par,
                                                 abortw)
                                    : gather_h<false, kNP>(gran + (long long)(i + 1) * G, hg + i + 1, i + 1, G, err, par,
                                                      abortw));
     stamp(i + 1, 1);
-    if (ub == 0 && threadIdx.x == 0) {                       // as k_arnoldi_finalize
-        const int ld = m + 1;
-        double *Hc = H + i * ld;
-        Hc[i + 1] = hn;
-        for (int k = 0; k < i; k++) apply_rot(Hc[k], Hc[k + 1], cs[k], sn[k]);
-        double c, sv;
-        gen_rot(Hc[i], Hc[i + 1], c, sv);
-        cs[i] = c;
-        sn[i] = sv;
-        apply_rot(Hc[i], Hc[i + 1], c, sv);
-        apply_rot(s[i], s[i + 1], c, sv);
-        const double resid = fabs(s[i + 1]) / ds->normb;
-        hist[ds->hist_len + i] = resid;
-        ds->resid = resid;
-        if (resid < ds->tol) {
-            ds->conv_i = i;
-            ds->done = DONE_INNER;
-        }
+    if (ub == 0 && threadIdx.x == 0) {                       // rotations 0..i-1 are applied: registers, then stores
+        givens_finish(hlo, hn, gin, i, Hc, cs, sn, s, hist, ds);
+        stamp_ht(4);
     }
     const double inv = (hn != 0.0) ? 1.0 / hn : 0.0;
     double *vout = V + (long long)(i + 1) * ldv;
@@ -4604,6 +4681,10 @@ __global__ __launch_bounds__(kBlock) void k_arnoldi_persist(Gate g, int i, int m
             if (2 * u < nfill) fill[2 * u] = kSentinel;
             if (2 * u + 1 < nfill) fill[2 * u + 1] = kSentinel;
         }
+    }
+    if (trow == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (diagnostics only) the stores performed
+        stamp_ht(5);
     }
 }
 
@@ -4821,27 +4902,9 @@ __global__ __launch_bounds__(kBlock, 3) void k_arnoldi_persist2(Gate g, long lon
     for (int q = 0; q < 2; q++) {
         if (!act[q]) continue;
         const double hq = sqrt(hn[q]);
-        if (ub == 0 && threadIdx.x == 0) {                        // as k_arnoldi_finalize
-            DevState *d = dsq[q];
-            const int ld = m + 1;
-            double *Hc = zp(H, zs, q) + i * ld;
-            double *csq = zp(cs, zs, q), *snq = zp(sn, zs, q), *sq = zp(s, zs, q);
-            Hc[i + 1] = hq;
-            for (int k = 0; k < i; k++) apply_rot(Hc[k], Hc[k + 1], csq[k], snq[k]);
-            double c, sv;
-            gen_rot(Hc[i], Hc[i + 1], c, sv);
-            csq[i] = c;
-            snq[i] = sv;
-            apply_rot(Hc[i], Hc[i + 1], c, sv);
-            apply_rot(sq[i], sq[i + 1], c, sv);
-            const double resid = fabs(sq[i + 1]) / d->normb;
-            zp(hist, zs, q)[d->hist_len + i] = resid;
-            d->resid = resid;
-            if (resid < d->tol) {
-                d->conv_i = i;
-                d->done = DONE_INNER;
-            }
-        }
+        if (ub == 0 && threadIdx.x == 0)                          // the column from memory, batched loads
+            givens_column(i, hq, zp(H, zs, q) + i * (m + 1), zp(cs, zs, q), zp(sn, zs, q), zp(s, zs, q),
+                          zp(hist, zs, q), dsq[q]);
         const double inv = (hq != 0.0) ? 1.0 / hq : 0.0;
         double *vout = Vq[q] + (long long)(i + 1) * ldv;
 #pragma unroll
@@ -4991,25 +5054,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_arnoldi_wide(Gate g, int i, int m
         publish(k + 1, acc);
     }
     const double hn = sqrt(gather_h<true>(gran + (long long)(i + 1) * G, hg + i + 1, i + 1, G, err, gpar, abortw));
-    if (blockIdx.x == 0 && threadIdx.x == 0) {               // as k_arnoldi_finalize
-        const int ld = m + 1;
-        double *Hc = H + i * ld;
-        Hc[i + 1] = hn;
-        for (int k = 0; k < i; k++) apply_rot(Hc[k], Hc[k + 1], cs[k], sn[k]);
-        double c, sv;
-        gen_rot(Hc[i], Hc[i + 1], c, sv);
-        cs[i] = c;
-        sn[i] = sv;
-        apply_rot(Hc[i], Hc[i + 1], c, sv);
-        apply_rot(s[i], s[i + 1], c, sv);
-        const double resid = fabs(s[i + 1]) / ds->normb;
-        hist[ds->hist_len + i] = resid;
-        ds->resid = resid;
-        if (resid < ds->tol) {
-            ds->conv_i = i;
-            ds->done = DONE_INNER;
-        }
-    }
+    // (the column from memory, as the per-step kernels: an on-chip column would
+    // cost this kernel registers it does not have)
+    if (blockIdx.x == 0 && threadIdx.x == 0) givens_column(i, hn, H + i * (m + 1), cs, sn, s, hist, ds);
     const double inv = (hn != 0.0) ? 1.0 / hn : 0.0;
     double2 *vout = reinterpret_cast<double2 *>(V + (long long)(i + 1) * ldv);
 #pragma unroll

@@ -1095,7 +1095,9 @@ UnitMap unit_map(const gg_solver *s)
 
 // diagnostics: GG_MGS_TRACE=N -- device time stamps of the N-th persistent
 // orthogonalization launch (k_arnoldi_persist: per step start / h known /
-// partial formed / published, for unit-block 0 and XCD 0's reducer)
+// partial formed / published, for unit-block 0 and XCD 0's reducer; row 2:
+// unit-block 0's head and tail -- entry, gate / abort / election resolved, w
+// and v_0 landed | the Givens block done, v_{i+1} stored)
 long long *mgs_trace_for(gg_solver *s, int i, int m)
 {
     static const long long at = [] {
@@ -1103,7 +1105,7 @@ long long *mgs_trace_for(gg_solver *s, int i, int m)
         return e ? atoll(e) : -1LL;
     }();
     if (at < 0 || (long long)s->mgs_seq + 1 != at) return nullptr;
-    s->mgs_trace.alloc((size_t)2 * (m + 2) * 4);
+    s->mgs_trace.alloc((size_t)3 * (m + 2) * 4);
     GG_HIP(hipMemsetAsync(s->mgs_trace.p, 0, s->mgs_trace.n * sizeof(long long), s->st));
     s->mgs_trace_i = i;
     return s->mgs_trace.p;
@@ -1112,10 +1114,10 @@ void mgs_trace_print(gg_solver *s)
 {
     if (s->mgs_trace_i < 0) return;
     const int i = s->mgs_trace_i;
-    std::vector<long long> h((size_t)2 * (i + 2) * 4);
+    std::vector<long long> h((size_t)3 * (i + 2) * 4);
     GG_HIP(hipMemcpy(h.data(), s->mgs_trace.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    for (int row = 0; row < 2; row++)
-        for (int k = 0; k <= i + 1; k++) {
+    for (int row = 0; row < 3; row++)
+        for (int k = 0; k <= (row == 2 ? 1 : i + 1); k++) {
             const long long *t = &h[((size_t)row * (i + 2) + k) * 4];
             std::fprintf(stderr, "mgs_trace i=%d row=%d k=%d %lld %lld %lld %lld\n", i, row, k, t[0], t[1], t[2], t[3]);
         }

@@ -14,7 +14,7 @@ for line in open(sys.argv[1]):
     i_seen = i
     rows[(row, k)] = [int(m.group(j)) for j in range(4, 8)]
 us = lambda t: t / 100.0
-print(f"GG_MGS_TRACE=540 (C2, bench --steps 1 --warmup 0): k_arnoldi_persist at inner index i = {i_seen},")
+print(f"GG_MGS_TRACE (C2, bench --steps 1 --warmup 0): k_arnoldi_persist at inner index i = {i_seen},")
 print("device s_memrealtime stamps (100 MHz) per MGS step k: start, h known (all-gather done), partial formed, partial published.")
 print("row 0 = unit-block 0, row 1 = the elected reducer of XCD 0.  Times in microseconds.")
 print()
@@ -39,3 +39,20 @@ for k in ks:
 if g:
     print()
     print(f"mean over steps 1..{ks[-1] - 1}: gather {sum(g) / len(g):.2f} us, step {sum(s) / len(s):.2f} us")
+# row 2: unit-block 0's head and tail -- k 0: entry, gate / abort / election
+# resolved, w and v_0 landed; k 1: the Givens block done, v_{i+1} stored
+hd, tl = rows.get((2, 0)), rows.get((2, 1))
+if hd and tl and hd[0] > 0 and tl[1] > 0:
+    first, last = rows[(0, ks[0])], rows[(0, ks[-1])]
+    d = lambda a, b: us(b - a)
+    print()
+    print("head and tail of the launch (unit-block 0, thread 0), microseconds:")
+    print(f"  head  entry -> gate / abort / election resolved {d(hd[0], hd[1]):6.2f}")
+    print(f"        -> w and v_0 landed                      {d(hd[1], hd[2]):6.2f}")
+    print(f"        -> <w, v_0> published, step 0 starts     {d(hd[2], first[0]):6.2f}")
+    print(f"        head in all (entry -> step 0)            {d(hd[0], first[0]):6.2f}")
+    print(f"  steps step 0 -> the norm gathered               {d(first[0], last[1]):6.2f}")
+    print(f"  tail  the norm gathered -> Givens block done    {d(last[1], tl[0]):6.2f}")
+    print(f"        -> the block's v_{{i+1}} stores performed   {d(tl[0], tl[1]):6.2f}")
+    print(f"        tail in all                              {d(last[1], tl[1]):6.2f}")
+    print(f"  launch (entry -> last store)                    {d(hd[0], tl[1]):6.2f}")
