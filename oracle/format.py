@@ -39,13 +39,18 @@ def coo2csr_in(nrows, a, i_idx, j_idx):
             init += 1
     rp = [0] + [row_start[r] for r in range(nrows)]
     for r in range(nrows):
-        lb, ub = rp[r], rp[r + 1]
-        for top in range(ub - 1, lb, -1):
-            for k in range(lb, top):
-                if jj[k] > jj[k + 1]:
-                    a[k], a[k + 1] = a[k + 1], a[k]
-                    jj[k], jj[k + 1] = jj[k + 1], jj[k]
+        sort(jj, a, rp[r], rp[r + 1])
     return np.array(rp, np.int64), np.array(jj, np.int64), np.array(a)
+
+
+def sort(col_idx, a, start, end):
+    """sort / sortDouble (:66-106): bubble sort of [start, end) by column, in
+    place on two lists; equal columns keep their order"""
+    for top in range(end - 1, start, -1):
+        for k in range(start, top):
+            if col_idx[k] > col_idx[k + 1]:
+                a[k], a[k + 1] = a[k + 1], a[k]
+                col_idx[k], col_idx[k + 1] = col_idx[k + 1], col_idx[k]
 
 
 def csc2csr(m, p, i, x):

@@ -9,12 +9,21 @@
  * double precision (the reference computes in float).
  * Reference paths are relative to the upstream tree (sheldonucr/GPU-GMRES).
  *
- * Parity status: the reference's own tests pin no GMRES residual history
- * (SURVEY.md Sec. 4, 8(c)); building/running the reference was refused in
- * this environment.  The restatement is therefore
- * checked against the reference's data fixtures (cusp laplacian/random
- * matrices, sherman1) through independent numpy/scipy computations
- * (tests/golden/make_golden.py) -- see DESIGN.md "Oracle".
+ * Parity status.  Pinned to the reference's OWN code, bit for bit: the four
+ * routines that live in plain C++ files -- orc_spmv (computeSpMV), orc_lusolve
+ * in division mode 0 (LUSolve_ignoreZero), orc_iluk at levels 0-2 (lofC +
+ * ilukC) and oracle/format.py (coo2csrDouble_in, sortDouble, LDcsc2csr,
+ * LDcsc2csrMySpMatrixDouble).  oracle/Makefile builds those files from the
+ * reference checkout into _ref/libgg_ref.so (float read as double, contraction
+ * off; ref_widen.h, ref_shim.cpp, ref.py), tests/golden/ref_pins.npz records
+ * what they compute, tests/test_ref_pins.py holds this file to it.
+ * Still unpinned, because they live in CUDA files that cannot be built here
+ * (SURVEY.md Sec. 8(c)): orc_ilu0 (leftILU), the split maps, the source
+ * waveforms and the GMRES engines; the reference's own tests pin no residual
+ * history.  Those are checked against the reference's
+ * data fixtures (cusp laplacian/random matrices, sherman1) through independent
+ * numpy/scipy computations (tests/golden/make_golden.py) -- see DESIGN.md
+ * "Oracle".
  */
 #ifndef GG_ORACLE_H_
 #define GG_ORACLE_H_
