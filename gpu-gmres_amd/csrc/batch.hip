@@ -202,12 +202,12 @@ void enqueue_init_b(const Ctx &c)
     const BatchWs &a = *c.B;
     Gate none;
     batch_minv(s, a.arena, none, a.bv, a.t1, a.bb);                                 // bb = M b
-    launch_dot_b(none, a.bb, a.bb, a.pA, c.G, c.P, c.S, c.zs, s->st);
-    launch_set_normb_b(a.pA, c.G, a.ds, c.S, c.zs, s->st);
+    launch_dot(none, a.bb, a.bb, a.pA, c.G, c.P, s->st, Batch{c.S, c.zs});
+    launch_set_normb(a.pA, c.G, a.ds, s->st, Batch{c.S, c.zs});
     launch_spmv_b(none, s->dA, a.xv, a.bv, a.rr, true, c.S, c.zs, s->st);        // rr = b - A x
     batch_minv(s, a.arena, none, a.rr, a.t1, a.r);                                  // r = M rr
-    launch_dot_b(none, a.r, a.r, a.pA, c.G, c.P, c.S, c.zs, s->st);
-    launch_init_beta_b(a.pA, c.G, a.ds, a.hist, c.S, c.zs, s->st);
+    launch_dot(none, a.r, a.r, a.pA, c.G, c.P, s->st, Batch{c.S, c.zs});
+    launch_init_beta(a.pA, c.G, a.ds, a.hist, s->st, Batch{c.S, c.zs});
 }
 
 // inner iterations [i0, i1) of the cycle (src/gmres.cu:566-717's loop body:
@@ -253,15 +253,15 @@ void enqueue_iters_b(const Ctx &c, int i0, int i1)
             continue;
         }
         double *pin = a.pA, *pout = a.pB;
-        launch_dot_b(gi, a.w, a.V, pin, c.G, c.P, c.S, c.zs, s->st);            // <w, v_0>
+        launch_dot(gi, a.w, a.V, pin, c.G, c.P, s->st, Batch{c.S, c.zs});   // <w, v_0>
         for (int k = 0; k <= i; k++) {
             const double *vk = a.V + (long long)k * c.P;
             const double *vn = (k < i) ? a.V + (long long)(k + 1) * c.P : a.w;
-            launch_mgs_step_b(gi, i, k, c.m, a.w, vk, vn, pin, pout, a.H, c.G, c.P, c.S, c.zs, s->st);
+            launch_mgs_step(gi, i, k, c.m, a.w, vk, vn, pin, pout, a.H, c.G, c.P, s->st, Batch{c.S, c.zs});
             std::swap(pin, pout);
         }
-        launch_arnoldi_finalize_b(gi, i, c.m, a.ds, pin, c.G, a.w, a.V + (long long)(i + 1) * c.P, a.H, a.cs, a.sn,
-                                  a.sv, a.hist, c.P, c.S, c.zs, s->st);
+        launch_arnoldi_finalize(gi, i, c.m, a.ds, pin, c.G, a.w, a.V + (long long)(i + 1) * c.P, a.H, a.cs, a.sn,
+                                a.sv, a.hist, c.P, s->st, Batch{c.S, c.zs});
     }
 }
 
@@ -273,14 +273,14 @@ void enqueue_tail_b(const Ctx &c)
     Gate gu;
     gu.done = &a.ds->done;
     gu.mask = DONE_RESTART | DONE_INIT | DONE_ABORT | DONE_FINAL | DONE_EXH;
-    launch_update_b(gu, c.m, a.ds, a.H, a.sv, a.y, a.V, c.P, a.xv, c.G, c.P, c.um, c.S, c.zs, s->st);
+    launch_update(gu, c.m, a.ds, a.H, a.sv, a.y, a.V, c.P, a.xv, c.G, c.P, s->st, c.um, Batch{c.S, c.zs});
     Gate gr;
     gr.done = &a.ds->done;
     gr.mask = ~0;
     launch_spmv_b(gr, s->dA, a.xv, a.bv, a.rr, true, c.S, c.zs, s->st);
     batch_minv(s, a.arena, gr, a.rr, a.t1, a.r);
-    launch_dot_b(gr, a.r, a.r, a.pA, c.G, c.P, c.S, c.zs, s->st);
-    launch_end_cycle_b(a.pA, c.G, a.ds, a.hist, c.S, c.zs, s->st);
+    launch_dot(gr, a.r, a.r, a.pA, c.G, c.P, s->st, Batch{c.S, c.zs});
+    launch_end_cycle(a.pA, c.G, a.ds, a.hist, s->st, Batch{c.S, c.zs});
 }
 
 int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, double *d_x, long long ldx,
@@ -314,10 +314,10 @@ int solve_batch_once(gg_solver *s, int S, const double *d_b, long long ldb, doub
     for (const Track &t : tr) left += !t.fin;
     while (left > 0) {
         // ---- one restart cycle, in chunks of K inner iterations
-        launch_init_cycle_b(a.ds, a.r, a.V, a.sv, c.G, c.P, S, c.zs, st);
+        launch_init_cycle(a.ds, a.r, a.V, a.sv, c.G, c.P, st, Batch{S, c.zs});
         if (a.persist) {
-            launch_fill_u64_b(a.gran, a.ngran, kSentinel, S, c.zs, st);
-            launch_fill_u64_b(a.xgran, a.nxgran, kSentinel, S, c.zs, st);
+            launch_fill_u64(a.gran, a.ngran, kSentinel, st, Batch{S, c.zs});
+            launch_fill_u64(a.xgran, a.nxgran, kSentinel, st, Batch{S, c.zs});
         }
         for (Track &t : tr) t.cyc_over = t.fin;
         int issued = 0;

@@ -223,8 +223,8 @@ void stage_in(gg_solver *s, const BatchArena &A, const double *d_b, long long ld
     if (!s->err.p) s->err.alloc(1);
     launch_gather_b(d_b, ldb * 8, s->lay2nat.p, bv, A.zs, s->Ppad, A.S, st);
     launch_gather_b(d_x, ldx * 8, s->lay2nat.p, xv, A.zs, s->Ppad, A.S, st);
-    launch_fill_u64_b(A.Lg, s->L.wl.ngran(), kSentinel, A.S, A.zs, st);
-    launch_fill_u64_b(A.Ug, s->U.wl.ngran(), kSentinel, A.S, A.zs, st);
+    launch_fill_u64(A.Lg, s->L.wl.ngran(), kSentinel, st, Batch{A.S, A.zs});
+    launch_fill_u64(A.Ug, s->U.wl.ngran(), kSentinel, st, Batch{A.S, A.zs});
     init_states();
     GG_HIP(hipMemsetAsync(s->err.p, 0, sizeof(int), st));
     GG_HIP(hipEventRecord(s->ev0, st));

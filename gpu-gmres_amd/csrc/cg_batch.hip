@@ -7,11 +7,11 @@
 // own, q * zs bytes after scenario 0's, and an iteration is seven launches for
 // all scenarios together --
 //   launch_spmv_b     q = A p         (A's entries read once per 8 scenarios)
-//   launch_cg_pq_b    partials of p . q
-//   launch_cg_xr_b    alpha; x = alpha p + x; r = (-alpha) q + r
+//   launch_cg_pq      partials of p . q
+//   launch_cg_xr      alpha; x = alpha p + x; r = (-alpha) q + r
 //   launch_trsv_b L, U   z = M r      (one wavefront dependency chain for all)
-//   launch_cg_rz_b    partials of r . z and z . z
-//   launch_cg_p_b     res, beta; p = beta p + z
+//   launch_cg_rz      partials of r . z and z . z
+//   launch_cg_p       res, beta; p = beta p + z
 // Per scenario the arithmetic is the single solve's -- the same kernels with a
 // scenario offset -- so scenario q's status, count, history and solution are
 // bit-identical to gg_solve_device(GG_SOLVE_CG) on that right-hand side alone.
@@ -117,12 +117,12 @@ void enqueue_start_b(const Ctx &c)
     const CgBatchWs &a = *c.B;
     const Gate none;
     batch_minv(s, a.arena, none, a.b, a.t1, a.bb);                                  // bb = M b
-    launch_dot_b(none, a.bb, a.bb, a.part, c.G, c.P, c.S, c.zs, s->st);
-    launch_normb_b(a.part, c.G, &a.cs->normb, c.S, c.zs, s->st);
+    launch_dot(none, a.bb, a.bb, a.part, c.G, c.P, s->st, Batch{c.S, c.zs});
+    launch_normb(a.part, c.G, &a.cs->normb, s->st, Batch{c.S, c.zs});
     launch_spmv_b(none, s->dA, a.x, a.b, a.r, true, c.S, c.zs, s->st);              // r = b - A x
     batch_minv(s, a.arena, none, a.r, a.t1, a.z);                                   // z = M r
-    launch_cg_rz_b(none, a.r, a.z, a.part + 1024, c.G, c.P, c.S, c.zs, s->st);
-    launch_cg_p_b(none, 0, true, a.cs, a.part + 1024, c.G, a.p, a.z, a.hist, c.P, c.S, c.zs, s->st);   // p = z
+    launch_cg_rz(none, a.r, a.z, a.part + 1024, c.G, c.P, s->st, Batch{c.S, c.zs});
+    launch_cg_p(none, 0, true, a.cs, a.part + 1024, c.G, a.p, a.z, a.hist, c.P, s->st, Batch{c.S, c.zs});   // p = z
 }
 
 // Cg::enqueue_iterations for every scenario, each launch gated per scenario
@@ -137,11 +137,11 @@ void enqueue_iterations_b(const Ctx &c, int k0, int k1)
         g.nit = &a.cs->max_iter;
         g.i = k;
         launch_spmv_b(g, s->dA, a.p, nullptr, a.q, false, c.S, c.zs, s->st);        // q = A p
-        launch_cg_pq_b(g, a.p, a.q, a.part, c.G, c.P, c.S, c.zs, s->st);
-        launch_cg_xr_b(g, k, a.cs, a.part, c.G, a.x, a.p, a.r, a.q, c.P, c.S, c.zs, s->st);
+        launch_cg_pq(g, a.p, a.q, a.part, c.G, c.P, s->st, Batch{c.S, c.zs});
+        launch_cg_xr(g, k, a.cs, a.part, c.G, a.x, a.p, a.r, a.q, c.P, s->st, Batch{c.S, c.zs});
         batch_minv(s, a.arena, g, a.r, a.t1, a.z);                                  // z = M r
-        launch_cg_rz_b(g, a.r, a.z, a.part + 1024, c.G, c.P, c.S, c.zs, s->st);
-        launch_cg_p_b(g, k, false, a.cs, a.part + 1024, c.G, a.p, a.z, a.hist, c.P, c.S, c.zs, s->st);
+        launch_cg_rz(g, a.r, a.z, a.part + 1024, c.G, c.P, s->st, Batch{c.S, c.zs});
+        launch_cg_p(g, k, false, a.cs, a.part + 1024, c.G, a.p, a.z, a.hist, c.P, s->st, Batch{c.S, c.zs});
     }
 }
 

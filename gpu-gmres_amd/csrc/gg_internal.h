@@ -156,7 +156,7 @@ void relabel_tri(const CanonTri &C, const std::vector<long long> &nat2lay, Canon
 //   slot = ((band*(T/2) + t/2)*64 + l)*2 + t%2     (a lane's step pair adjacent)
 //   T = nx + 63 rounded up to a multiple of 64 (four 16-step kernel batches)
 // steps per band are padded to a multiple of this (whole batches, an even
-// number of them for the two-deep boundary polls; kernels.hip checks it)
+// number of them for the two-deep boundary polls; kernels/trsv_wave.hip checks it)
 constexpr int kWaveTAlign = 32;
 // 3D tiles: steps per tile padded to whole pairs of 8-step batches (k_trsv_tile3d)
 constexpr int kTileTAlign = 16;
@@ -176,7 +176,7 @@ struct Wave2D {
     bool u_inline_first = false;
     long long P2 = 0;        // one plane's layout length (nbands * T * 64)
     long long P = 0;         // padded layout length (nz * P2)
-    // 3D tile layout (tile = true; kernels.hip k_trsv_tile3d): a wave owns a
+    // 3D tile layout (tile = true; kernels/trsv_wave.hip k_trsv_tile3d): a wave owns a
     // tile of 8 lines x 8 planes, lane l = a + 8*g(c) for line j = 8J + a,
     // plane k = 8K + c, with the Gray code g(c) = c ^ (c >> 1): consecutive
     // planes sit in half-rows that differ in one bit, i.e. one DPP row_ror:8,
@@ -363,7 +363,7 @@ struct DevTri {
     DBuf<unsigned long long> prog;   // 3D: per (plane, band) batches stored (0 between launches)
     DBuf<int> order;             // 3D tiles: forward dependency order (the backward solve reverses it)
     bool il = false;             // upper 2D: in-line term first (Wave2D::u_inline_first)
-    int div = WD_UNIT;           // division mode (kernels.hip k_trsv_wave2d)
+    int div = WD_UNIT;           // division mode (kernels/trsv_wave.hip k_trsv_wave2d)
     bool rcp_ok = false;         // every divisor admits WD_RCP
     bool mul_ok = false;         // every 1/d is finite and normal (WD_MUL admissible; rw uploaded)
     bool fma_ok = false;         // unskewed 2D grid / 3D tiles, canonical order, unit L or mul_ok U (c*s uploaded)

@@ -1,4 +1,4 @@
-// kernels.h -- launchers for the hand-written gfx950 kernels of the GMRES path.
+// kernels.h -- launchers for the hand-written gfx950 kernels of the GMRES path (kernels.hip, kernels/*.hip).
 #pragma once
 
 #include "gg_internal.h"
@@ -50,13 +50,23 @@ struct UnitMap {
     long long tbase = 0, tn = 0;
 };
 
+// The many-RHS batch (batch.hip, cg_batch.hip) runs the launchers that take a
+// Batch on a grid (G, nsc), blockIdx.y = scenario: scenario q's per-scenario
+// buffers (vectors, partials, H, Givens, history, control block, hand-off
+// granules; the gate's done / nit likewise) lie q * zs bytes after scenario
+// 0's.  Same kernels and per-scenario arithmetic; the default is the single solve.
+struct Batch {
+    int nsc = 1;
+    long long zs = 0;
+};
+
 constexpr int kBlock = 256;
 constexpr unsigned long long kSentinel = 0x7FF4DEAD0000BEEFull;  // sNaN payload: "not ready"
 
 int reduce_grid(long long units);  // blocks for the vector kernels (units = Ppad/2)
 
 // ---- vector ops (lengths are Ppad, a multiple of 512) --------------------
-void launch_fill_u64(unsigned long long *p, long long n, unsigned long long v, hipStream_t st);
+void launch_fill_u64(unsigned long long *p, long long n, unsigned long long v, hipStream_t st, Batch bt = {});
 // transient step: u = sources(it*h) (DC / PULSE / PWL); w = B u + (C/h) x   (natural order, n rows)
 void launch_transient_step(int n, int nsrc, const int *kind, const int *dptr, const double *data, int it,
                            double h, double *u, const int *src_ptr, const int *src_idx, const double *cdiag,
@@ -86,7 +96,8 @@ void launch_iluk_wave(int n, const long long *prow, const int *nl, const int *pc
 void launch_gather(const double *in, const long long *idx, double *out, long long n, hipStream_t st,
                    double *fill0 = nullptr, double *fill1 = nullptr, long long nfill = 0);
 void launch_copy(const double *in, double *out, long long n, hipStream_t st);
-void launch_dot(Gate g, const double *a, const double *b, double *part, int G, long long Ppad, hipStream_t st);
+void launch_dot(Gate g, const double *a, const double *b, double *part, int G, long long Ppad, hipStream_t st,
+                Batch bt = {});
 
 // ---- sharded solve (dd.hip) --------------------------------------------------
 // out[r] = in[r] - sum_k C.v[k] * x[C.ci[k]] (sequential, listed order), r < C.n
@@ -250,18 +261,18 @@ int wave_batch_steps(int div, bool d3 = false, int skew = 1);   // steps per bat
 int tile_batch_steps();                                          // steps per batch of the 3D tile kernel
 
 // ---- GMRES scalar / MGS kernels ----------------------------------------------
-void launch_set_normb(const double *part, int G, DevState *ds, hipStream_t st);
-void launch_init_beta(const double *part, int G, DevState *ds, double *hist, hipStream_t st);
+void launch_set_normb(const double *part, int G, DevState *ds, hipStream_t st, Batch bt = {});
+void launch_init_beta(const double *part, int G, DevState *ds, double *hist, hipStream_t st, Batch bt = {});
 void launch_init_cycle(DevState *ds, const double *r, double *v0, double *s, int G, long long Ppad,
-                       hipStream_t st);
+                       hipStream_t st, Batch bt = {});
 void launch_mgs_step(Gate g, int i, int k, int m, double *w, const double *vk, const double *vnext,
                      const double *part_in, double *part_out, double *H, int G, long long Ppad,
-                     hipStream_t st);
+                     hipStream_t st, Batch bt = {});
 // the same with a separate dot range [0, Pdot) and nparts_in input partials
 // (the sharded solve: every shard's block partials after the all-gather)
 void launch_mgs_step_r(Gate g, int i, int k, int m, double *w, const double *vk, const double *vnext,
                        const double *part_in, int nparts_in, double *part_out, double *H, int G,
-                       long long Ppad, long long Pdot, hipStream_t st);
+                       long long Ppad, long long Pdot, hipStream_t st, Batch bt = {});
 // CGS2 (sharded solve, GG_SOLVE_CGS2): block partials of <w, v_k>, k < nk, at
 // part[k*G + b]; every shard's partials of dot k summed into h[k] (shard q's
 // slot at part + q*cnt) and into H[k, i] (add: +=); w -= sum_k h[k] v_k with
@@ -279,10 +290,11 @@ bool launch_cgs_update_dot(Gate g, double *w, const double *V, long long ldv, co
                            long long Ppad, long long Pdot, double *part, hipStream_t st);
 void launch_arnoldi_finalize_r(Gate g, int i, int m, DevState *ds, const double *part, int nparts_in,
                                int G, const double *w, double *vnext, double *H, double *cs,
-                               double *sn, double *s, double *hist, long long Ppad, hipStream_t st);
+                               double *sn, double *s, double *hist, long long Ppad, hipStream_t st,
+                               Batch bt = {});
 void launch_arnoldi_finalize(Gate g, int i, int m, DevState *ds, const double *part, int G,
                              const double *w, double *vnext, double *H, double *cs, double *sn,
-                             double *s, double *hist, long long Ppad, hipStream_t st);
+                             double *s, double *hist, long long Ppad, hipStream_t st, Batch bt = {});
 // persistent Arnoldi orthogonalization (one launch per inner iteration):
 // units per thread (1/2/4/8, 0 = too many), how many blocks can be resident
 int arnoldi_persist_units(int G, long long Ppad);
@@ -324,8 +336,8 @@ void launch_arnoldi_wide(Gate g, int i, int m, DevState *ds, const double *w, do
                          const UnitMap &um, hipStream_t st);
 void launch_update(Gate g, int m, DevState *ds, const double *H, const double *s, double *ysmall,
                    const double *V, long long ldv, double *acc, int G, long long Ppad, hipStream_t st,
-                   const UnitMap &um = UnitMap{});
-void launch_end_cycle(const double *part, int G, DevState *ds, double *hist, hipStream_t st);
+                   const UnitMap &um = UnitMap{}, Batch bt = {});
+void launch_end_cycle(const double *part, int G, DevState *ds, double *hist, hipStream_t st, Batch bt = {});
 
 // ---- conjugate gradients (GG_SOLVE_CG, cg.hip) -------------------------------
 // Device-side control block of a CG solve.  Every launch of an iteration is
@@ -347,19 +359,21 @@ constexpr int SR_CONV = 1, SR_BREAKDOWN = 2, SR_INIT = 4;
 // 0-based index.  launch_normb, launch_cg_pq and launch_cg_rz are shared with
 // BiCGStab (plain reductions, no control block):
 //   *normb = sqrt(sum of part) (0 -> 1); normb = &state->normb of either control block
-void launch_normb(const double *part, int G, double *normb, hipStream_t st);
+void launch_normb(const double *part, int G, double *normb, hipStream_t st, Batch bt = {});
 //   part = block partials of p . q
-void launch_cg_pq(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, hipStream_t st);
+void launch_cg_pq(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, hipStream_t st,
+                  Batch bt = {});
 //   pq = sum of part; not pq > 0: SR_BREAKDOWN; alpha = rz / pq; x = alpha p + x; r = (-alpha) q + r
 void launch_cg_xr(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
-                  const double *q, long long Ppad, hipStream_t st);
+                  const double *q, long long Ppad, hipStream_t st, Batch bt = {});
 //   part = block partials of r . z, then of z . z
-void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, hipStream_t st);
+void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, hipStream_t st,
+                  Batch bt = {});
 //   rzn, zz = sums of part; resid = hist[it + 1] = sqrt(zz) / normb; resid < tol: SR_CONV; else not
 //   rzn > 0: SR_BREAKDOWN; else p = (rzn / rz) p + z.  start (the initial residual, nothing
 //   counted): hist[0], resid <= tol: SR_INIT, p = z
 void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
-                 double *hist, long long Ppad, hipStream_t st);
+                 double *hist, long long Ppad, hipStream_t st, Batch bt = {});
 
 // ---- BiCGStab (GG_SOLVE_BICGSTAB, bicgstab.hip) ------------------------------
 // Device-side control block of a BiCGStab solve, gated like CgState.  alpha
@@ -392,17 +406,15 @@ void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, 
 void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
                  const double *r, double *rt, double *hist, long long Ppad, hipStream_t st);
 
-// ---- batched (many-RHS) launches, kernels.hip: nsc scenarios per launch,
-// scenario q's per-scenario buffers (vectors, partials, H, Givens, history,
-// control block, hand-off granules) q * zs bytes after scenario 0's; the gate's
-// done / nit likewise.  Same kernels and per-scenario arithmetic as above.
+// ---- batched (many-RHS) launches with kernels or loops of their own (the rest
+// of the batch runs the launchers above with a Batch): nsc scenarios per launch,
+// scenario q's per-scenario buffers q * zs bytes after scenario 0's
 constexpr int kBatchSpmv = 8;     // scenarios per batched SpMV launch (A read once for them)
-void launch_fill_u64_b(unsigned long long *p, long long n, unsigned long long v, int nsc, long long zs,
-                       hipStream_t st);
 // out_q[i] = idx[i] < 0 ? 0 : in_q[idx[i]]  (in / out strides zin / zout bytes)
 void launch_gather_b(const double *in, long long zin, const long long *idx, double *out, long long zout,
                      long long n, int nsc, hipStream_t st);
 void launch_init_state_b(DevState *ds, long long zs, int nsc, double tol, int max_iter, int m, hipStream_t st);
+void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st);
 // out[q] = scenario q's control block (DevState or CgState), q < nsc; the int at out + nsc = *err
 template <class State>
 void launch_pack_states_b(const State *st0, long long zs, int nsc, State *out, const int *err, hipStream_t st);
@@ -420,37 +432,8 @@ void launch_spmv_b(Gate g, const DevCsr &A, const double *x, const double *b, do
 // trsv_b_granules(T) words per scenario, armed); trsv_batchable: T admits it
 bool trsv_batchable(const DevTri &T);
 long long trsv_b_granules(const DevTri &T);
-int batch_zmap();   // GG_BATCH_ZMAP: workgroup -> (scenario, band) placement (kernels.hip trsv_wave2d_body)
+int batch_zmap();   // GG_BATCH_ZMAP: workgroup -> (scenario, band) placement (kernels/trsv_wave.hip trsv_wave2d_body)
 void launch_trsv_b(Gate g, DevTri &T, const double *b, double *x, unsigned long long *bnd, int *err, int nsc,
                    long long zs, hipStream_t st);
-void launch_dot_b(Gate g, const double *a, const double *b, double *part, int G, long long Ppad, int nsc,
-                  long long zs, hipStream_t st);
-void launch_set_normb_b(const double *part, int G, DevState *ds, int nsc, long long zs, hipStream_t st);
-void launch_init_beta_b(const double *part, int G, DevState *ds, double *hist, int nsc, long long zs, hipStream_t st);
-void launch_init_cycle_b(DevState *ds, const double *r, double *v0, double *s, int G, long long Ppad, int nsc,
-                         long long zs, hipStream_t st);
-void launch_mgs_step_b(Gate g, int i, int k, int m, double *w, const double *vk, const double *vnext,
-                       const double *part_in, double *part_out, double *H, int G, long long Ppad, int nsc,
-                       long long zs, hipStream_t st);
-void launch_arnoldi_finalize_b(Gate g, int i, int m, DevState *ds, const double *part, int G, const double *w,
-                               double *vnext, double *H, double *cs, double *sn, double *s, double *hist,
-                               long long Ppad, int nsc, long long zs, hipStream_t st);
-void launch_update_b(Gate g, int m, DevState *ds, const double *H, const double *s, double *ysmall, const double *V,
-                     long long ldv, double *acc, int G, long long Ppad, const UnitMap &um, int nsc, long long zs,
-                     hipStream_t st);
-void launch_end_cycle_b(const double *part, int G, DevState *ds, double *hist, int nsc, long long zs, hipStream_t st);
-// the CG launches for nsc scenarios (cg_batch.hip): the kernels of launch_normb
-// and launch_cg_* on a grid (G, nsc), the control block, history and partials
-// per scenario like the vectors; the gate's done / nit = scenario 0's words
-void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st);
-void launch_normb_b(const double *part, int G, double *normb, int nsc, long long zs, hipStream_t st);
-void launch_cg_pq_b(Gate g, const double *p, const double *q, double *part, int G, long long Ppad, int nsc,
-                    long long zs, hipStream_t st);
-void launch_cg_xr_b(Gate g, int it, CgState *cs, const double *part, int G, double *x, const double *p, double *r,
-                    const double *q, long long Ppad, int nsc, long long zs, hipStream_t st);
-void launch_cg_rz_b(Gate g, const double *r, const double *z, double *part, int G, long long Ppad, int nsc,
-                    long long zs, hipStream_t st);
-void launch_cg_p_b(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
-                   double *hist, long long Ppad, int nsc, long long zs, hipStream_t st);
 
 }  // namespace gg

@@ -1056,7 +1056,7 @@ unsigned long long *hgran(gg_solver *s, int m, int i)
 }
 
 // The inner iteration's SpMV runs inside the forward solve's launch (FusedSpmv,
-// kernels.hip) on the 2D wavefront with GG_DIV_FMA's unit L; GG_FUSE_SPMV=0 keeps
+// kernels/trsv_wave.hip) on the 2D wavefront with GG_DIV_FMA's unit L; GG_FUSE_SPMV=0 keeps
 // the separate k_spmv_sell launch.  Same bits either way (the rows summed alike).
 bool fuse_spmv_active(gg_solver *s)
 {

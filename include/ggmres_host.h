@@ -107,7 +107,7 @@ int gg_host_wave3d(int n, const int *l_row_ptr, const int *l_col_idx, const doub
  * 4: 3D planes), nx, ny, nz, bands or tiles, steps per band T, tiles along
  * the lines NJ / planes NK, lane skew}; 0 when the layout is natural.
  * Replaces the level analysis cusparseScsrsv_analysis (src/gmres.cu:1516-1517)
- * for grid-shaped triangles (kernels.hip k_trsv_wave2d / k_trsv_tile3d). */
+ * for grid-shaped triangles (kernels/trsv_wave.hip k_trsv_wave2d / k_trsv_tile3d). */
 int gg_host_wave_layout(int n, const int *l_row_ptr, const int *l_col_idx, const double *l_val,
                         const int *u_row_ptr, const int *u_col_idx, const double *u_val,
                         long long *slot, int *info);

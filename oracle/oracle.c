@@ -348,7 +348,7 @@ int orc_iluk(int lofM, int n, const int *rp, const int *ci, const double *v,
  * 0 = x / d as the reference; 1 = x * (1.0 / d), the device's WD_MUL
  * (x = RN(acc * RN(1/d))), per triangle (L = the lower / Ml one, U = the upper
  * / Mr one).  Only for order-matched checks of GG_DIV_RCP solves.
- * 2 = the device's GG_DIV_FMA rows (kernels.hip WD_UFMA / WD_SFMA; orc_lusolve
+ * 2 = the device's GG_DIV_FMA rows (kernels/trsv_wave.hip WD_UFMA / WD_SFMA; orc_lusolve
  * and the split engine's two solves): with y = RN(1/d) (y = 1 for the unit L),
  * acc = RN(b*y) (b for the unit L), then for the off-diagonal terms nearest
  * first (|i - col| ascending) acc = fma(-RN(c*y), x[col], acc) (c for the unit L). */

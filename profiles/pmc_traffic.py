@@ -20,8 +20,9 @@ import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ["gpu-gmres_amd/csrc/kernels.hip", "gpu-gmres_amd/csrc/solver.hip",
-                  "gpu-gmres_amd/csrc/kernels.h", "gpu-gmres_amd/csrc/gg_internal.h"]
+KERNEL_SOURCES = ["gpu-gmres_amd/csrc/kernels.hip", "gpu-gmres_amd/csrc/kernels/device.h",
+                  "gpu-gmres_amd/csrc/kernels/host.h", "gpu-gmres_amd/csrc/kernels/trsv_wave.hip",
+                  "gpu-gmres_amd/csrc/solver.hip", "gpu-gmres_amd/csrc/kernels.h", "gpu-gmres_amd/csrc/gg_internal.h"]
 
 
 def src_sha():

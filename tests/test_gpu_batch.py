@@ -77,7 +77,7 @@ def test_solve_batch_bitexact_vs_single(grid, m, max_iter, tol, division):
 
 
 def test_solve_batch_long_restart_bitexact_vs_single():
-    """Restart lengths at the batch's other Update forms (launch_update_b):
+    """Restart lengths at the batch's other Update forms (launch_update with a Batch):
     m = 1 (k = 0 every cycle), m = 64 (lane 63 of the one-wave k_update_y) and
     m = 80 (k_update_y_serial, with the scenario stride), fixed-length runs of
     three scenarios -- a pair and a single for the two-scenario launches, one

@@ -3,7 +3,7 @@
 The reference divides every row of a non-unit triangle by its diagonal
 (LUSolve_ignoreZero, src/SpMV_compute.cpp:118-133; HostPrecond_left/right,
 src/preconditioner.cu:1094-1137).  GG_DIV_RCP has the wavefront solves compute
-x = RN(acc * RN(1/d)) instead (kernels.hip WD_MUL): within about one ulp per
+x = RN(acc * RN(1/d)) instead (kernels/trsv_wave.hip WD_MUL): within about one ulp per
 row, so it is a TOLERANCE mode.  Bars:
   * operators: bit-exact against the oracle restated with the same multiply
     (oracle.set_div_mode), and within 1e-13 (relative to the vector) of the
@@ -206,7 +206,7 @@ def test_rcp_c4_first_iterations(solver):
 # ---------------------------------------------------------------- GG_DIV_FMA
 # The 2D-grid (unskewed and, round 6, the skewed ILU(k) ones) and 3D-tile
 # wavefront solves as fused multiply-adds per row (nearest term first; U's b
-# and coefficients pre-scaled by RN(1/d), kernels.hip WD_UFMA / WD_SFMA),
+# and coefficients pre-scaled by RN(1/d), kernels/trsv_wave.hip WD_UFMA / WD_SFMA),
 # restated by oracle.set_div_mode(2, 2).  Bars as above:
 # bit-exact vs the order-matched restatement, within 1e-10 of the serial oracle
 # with the reference's arithmetic.

@@ -207,7 +207,7 @@ def test_ilu0_apply_bitexact(solver, name, force_level, monkeypatch):
 @pytest.mark.parametrize("hwdiv", [False, True])
 def test_wavefront_division_modes(solver, name, scale, hwdiv, monkeypatch):
     """The U solve divides by the diagonal: IEEE division (GG_WAVE_HWDIV=1) or
-    the reciprocal + two FMA corrections (kernels.hip WD_RCP).  Both must give
+    the reciprocal + two FMA corrections (kernels/trsv_wave.hip WD_RCP).  Both must give
     RN(acc/d) bit for bit; right-hand sides at 1e-250 / 1e250 leave WD_RCP's
     safe range, are flagged by the writer wave and redone with IEEE division."""
     if hwdiv:

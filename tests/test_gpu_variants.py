@@ -293,7 +293,7 @@ def test_anchor_flow(children, case):
             continue
         # Bbpc (GG_FLOW_LONG=0): every row with a term is a task of its own, a wave each, 4
         # waves a block -- more blocks than 4 on each of 256 CUs, so GG_FLOW_BPC decides the
-        # grid (kernels.hip launch_trsv_one: min(occupancy, bpc * CUs, tasks / 4)) ...
+        # grid (kernels.hip launch_trsv_levels: min(occupancy, bpc * CUs, tasks / 4)) ...
         tasks = int(np.count_nonzero(off > 0))
         assert tasks // 4 > 4 * 256
         # ... and few enough a level that the default is one block per CU (at most 4 waves

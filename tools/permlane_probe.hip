@@ -1,5 +1,5 @@
 // permlane_probe.hip -- checks the lane semantics of gfx950's v_permlane16_swap /
-// v_permlane32_swap as the 3D tile wavefront (kernels.hip k_trsv_tile3d) uses them.
+// v_permlane32_swap as the 3D tile wavefront (kernels/trsv_wave.hip k_trsv_tile3d) uses them.
 // Build: hipcc --offload-arch=gfx950 -O2 tools/permlane_probe.hip -o tools/permlane_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,5 +1,5 @@
 // Micro-benchmark: dependent-chain cycles per step of the 3D tile wavefront's
-// recurrence (kernels.hip k_trsv_tile3d) on gfx950, one wave: the plane shift
+// recurrence (kernels/trsv_wave.hip k_trsv_tile3d) on gfx950, one wave: the plane shift
 // (permlane swaps + selects), the line shift (DPP row_shr:1) and the full unit-L
 // step, against the 2D step.  Diagnostics only (not part of the library).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/tile_step_probe.hip -o tools/tile_step_probe
