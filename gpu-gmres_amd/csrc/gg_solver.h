@@ -149,7 +149,7 @@ struct gg_solver {
     bool vec_ok = false;  // the work vectors below are allocated for this space (ensure_vectors)
     DBuf<double> V, w, ww, r, rr, bb, t1, t2, z, xv, bv, y;
     DBuf<double> partA, partB, H, s, cs, sn, ysm;
-    // persistent Arnoldi orthogonalization (kernels.hip k_arnoldi_persist)
+    // persistent Arnoldi orthogonalization (kernels/arnoldi_persist.hip k_arnoldi_persist)
     bool persist = false;
     bool split_local = false;   // the split engine's vectors in a local layout (grid / RCM): its gathers are near
     bool wide = false;                  // k_arnoldi_wide (vectors beyond persist's registers)

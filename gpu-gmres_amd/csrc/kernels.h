@@ -55,6 +55,9 @@ struct UnitMap {
 // buffers (vectors, partials, H, Givens, history, control block, hand-off
 // granules; the gate's done / nit likewise) lie q * zs bytes after scenario
 // 0's.  Same kernels and per-scenario arithmetic; the default is the single solve.
+// The batch's own kernels and loops (the launch_*_b at the end) take nsc and zs
+// themselves: nsc scenarios per launch, one arena per scenario (solver.hip /
+// batch.hip).
 struct Batch {
     int nsc = 1;
     long long zs = 0;
@@ -295,11 +298,11 @@ void launch_arnoldi_finalize_r(Gate g, int i, int m, DevState *ds, const double 
 void launch_arnoldi_finalize(Gate g, int i, int m, DevState *ds, const double *part, int G,
                              const double *w, double *vnext, double *H, double *cs, double *sn,
                              double *s, double *hist, long long Ppad, hipStream_t st, Batch bt = {});
-// persistent Arnoldi orthogonalization (one launch per inner iteration):
+// persistent Arnoldi orthogonalization (kernels/arnoldi_persist.hip; one launch per inner iteration):
 // units per thread (1/2/4/8, 0 = too many), how many blocks can be resident
 int arnoldi_persist_units(int G, long long Ppad);
 int arnoldi_persist_max_blocks(int J);
-// xb: per inner step kMgsXcdWords words (the XCD-local gather's slots, kernels.hip
+// xb: per inner step kMgsXcdWords words (the XCD-local gather's slots, arnoldi_persist.hip
 // gather_xcd; re-armed with the granules), elect: kMgsElectWords words (zeroed
 // once), seq: strictly increasing per launch
 constexpr int kMgsXcdWords = 8 * 16, kMgsElectWords = 8 * 16;
@@ -339,7 +342,7 @@ void launch_update(Gate g, int m, DevState *ds, const double *H, const double *s
                    const UnitMap &um = UnitMap{}, Batch bt = {});
 void launch_end_cycle(const double *part, int G, DevState *ds, double *hist, hipStream_t st, Batch bt = {});
 
-// ---- conjugate gradients (GG_SOLVE_CG, cg.hip) -------------------------------
+// ---- conjugate gradients (GG_SOLVE_CG, cg.hip; kernels/short_recurrence.hip) ----
 // Device-side control block of a CG solve.  Every launch of an iteration is
 // gated on `done` (any bit) and on it < max_iter, so iterations enqueued past
 // the end of the solve do nothing.
@@ -375,7 +378,7 @@ void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G,
 void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
                  double *hist, long long Ppad, hipStream_t st, Batch bt = {});
 
-// ---- BiCGStab (GG_SOLVE_BICGSTAB, bicgstab.hip) ------------------------------
+// ---- BiCGStab (GG_SOLVE_BICGSTAB, bicgstab.hip; kernels/short_recurrence.hip) ----
 // Device-side control block of a BiCGStab solve, gated like CgState.  alpha
 // and omega are written by one launch and read by later ones; rho alternates
 // like CgState::rz (the launch that reads rho[it & 1] stores rho[(it + 1) & 1]).

@@ -200,6 +200,10 @@ __device__ __forceinline__ bool unit_real(const UnitMap &m, long long u)
     return t0 + 1 >= lo && t0 < lo + m.nx;
 }
 
+// 16-B units a thread of the streaming kernels (per-step GMRES, CG, BiCGStab)
+// loads per stream before it uses any
+constexpr int kUnroll = 4;
+
 __device__ __forceinline__ double2 ld2(const double *p, long long u)
 {
     return reinterpret_cast<const double2 *>(p)[u];
@@ -229,6 +233,22 @@ __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long 
 __device__ __forceinline__ void st_agent(unsigned long long *p, unsigned long long v)
 {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int ld_agent_i(const int *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent_i(int *p, int v)
+{
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double ld_agent_d(const double *p)
+{
+    return __longlong_as_double((long long)ld_agent(reinterpret_cast<const unsigned long long *>(p)));
+}
+__device__ __forceinline__ void st_agent_d(double *p, double v)
+{
+    st_agent(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v));
 }
 
 // 16 bytes stored write-through (two agent-scope 8-byte stores, sc1): visible

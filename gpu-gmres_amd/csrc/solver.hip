@@ -1397,7 +1397,7 @@ DevState read_state_checked(gg_solver *s)
 }
 
 // A persistent orthogonalization grid that was not co-resident aborted the
-// cycle (DONE_ABORT, kernels.hip gather_first): everything after the abort
+// cycle (DONE_ABORT, kernels/arnoldi_persist.hip gather_first): everything after the abort
 // point was gated off and x, r, j, hist_len are as before the cycle.  Restore
 // the control block (done = 0, resid = beta / normb as k_init_beta /
 // k_end_cycle left it), drop the persistent kernels for the solver's life and

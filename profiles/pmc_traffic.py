@@ -20,9 +20,10 @@ import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ["gpu-gmres_amd/csrc/kernels.hip", "gpu-gmres_amd/csrc/kernels/device.h",
-                  "gpu-gmres_amd/csrc/kernels/host.h", "gpu-gmres_amd/csrc/kernels/trsv_wave.hip",
-                  "gpu-gmres_amd/csrc/solver.hip", "gpu-gmres_amd/csrc/kernels.h", "gpu-gmres_amd/csrc/gg_internal.h"]
+KERNEL_DIR = "gpu-gmres_amd/csrc/kernels"
+KERNEL_SOURCES = [f"{KERNEL_DIR}/{f}" for f in sorted(os.listdir(os.path.join(REPO, KERNEL_DIR)))
+                  if f.endswith((".hip", ".h"))] + [
+    "gpu-gmres_amd/csrc/kernels.hip", "gpu-gmres_amd/csrc/solver.hip", "gpu-gmres_amd/csrc/kernels.h", "gpu-gmres_amd/csrc/gg_internal.h"]
 
 
 def src_sha():

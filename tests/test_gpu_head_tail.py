@@ -1,5 +1,5 @@
 """The orthogonalization launch's tail: the Hessenberg column rotated on chip as
-its entries arrive (kernels.hip givens_absorb / givens_finish / givens_column,
+its entries arrive (kernels/arnoldi.h givens_absorb / givens_finish / givens_column,
 the cs / sn preload of k_arnoldi_persist), and the launches gated off around it.
 
 Every case compares x, the result record (ret, iters, inner, restarts, relres)

@@ -2,7 +2,7 @@
 occupancy API"; ADVICE r3 on the fused SpMV's block order).
 
 * k_arnoldi_persist / k_arnoldi_wide: a launch whose blocks cannot all be
-  resident aborts its cycle (kernels.hip gather_first: DONE_ABORT), the host
+  resident aborts its cycle (kernels/arnoldi_persist.hip gather_first: DONE_ABORT), the host
   restores the control block and reruns the cycle on the per-step kernels --
   forced here with dynamic LDS (GG_PERSIST_TEST_LDS) so that fewer blocks fit
   than the grid has.  Results bit-identical to the per-step kernels and to the

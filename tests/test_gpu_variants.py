@@ -187,13 +187,13 @@ def assert_same_child(v, d, what):
 
 
 def units_per_thread(G, Ppad):
-    """kernels.hip arnoldi_persist_units"""
+    """kernels/arnoldi_persist.hip arnoldi_persist_units"""
     J = -(-(Ppad // 2) // (G * 256))
     return 1 if J <= 1 else 2 if J <= 2 else 4 if J <= 4 else 8 if J <= 8 else 0
 
 
 def persist_name(env, J):
-    """the instantiation GG_MGS_GATHER / GG_MGS_PREFETCH select (kernels.hip
+    """the instantiation GG_MGS_GATHER / GG_MGS_PREFETCH select (kernels/arnoldi_persist.hip
     persist_fn, stated on its own): prefetch 2 exists for the elected gather up
     to J = 4, the reducer-only blocks with a prefetch only"""
     g = int(env.get("GG_MGS_GATHER", 2))

@@ -137,7 +137,7 @@ def test_iluk_serial_pattern(ggmres_lib, case, monkeypatch):
     ("3", "0", 4, "k_arnoldi_persist<4, 2, 0>"), ("0", "2", 4, "k_arnoldi_persist<4, 0, 1>"),
     ("2", "2", 8, "k_arnoldi_persist<8, 2, 1>"), ("3", "2", 8, "k_arnoldi_persist<8, 3, 1>")])
 def test_mgs_kernel_names_the_instantiation_launched(ggmres_lib, monkeypatch, gather, prefetch, J, want):
-    """gg_mgs_kernel's name comes from the launch's own mapping (kernels.hip
+    """gg_mgs_kernel's name comes from the launch's own mapping (kernels/arnoldi_persist.hip
     persist_form), not from the environment's numbers -- host code, so J = 8,
     whose grid is not co-resident on an MI355X, is pinned here"""
     import ggmres
