@@ -103,6 +103,8 @@ def _load(path):
     L.orc_gmres_split.argtypes = ([ctypes.c_int, _i32p, _i32p, _f64p,
                                    ctypes.POINTER(SplitT)] + common)
     L.orc_gmres_split.restype = ctypes.c_int
+    L.orc_gmres_plain.argtypes = [ctypes.c_int, _i32p, _i32p, _f64p] + common
+    L.orc_gmres_plain.restype = ctypes.c_int
     _libs[path] = L
     _lib = L
 
@@ -299,6 +301,19 @@ def gmres_split(A, P, b, x0=None, m=32, max_iter=10000, tol=1e-7, hist_cap=None)
     mi, tl, hl, inner = ctypes.c_int(max_iter), ctypes.c_double(tol), ctypes.c_int(), ctypes.c_int()
     ret = lib().orc_gmres_split(A.n, A.rp, A.ci, A.v, ctypes.byref(P.s),
                                 np.ascontiguousarray(b, np.float64), x, int(m),
+                                ctypes.byref(mi), ctypes.byref(tl), hist, cap,
+                                ctypes.byref(hl), ctypes.byref(inner))
+    return _gmres_out(ret, x, mi, tl, hist, hl, inner)
+
+
+def gmres_plain(A, b, x0=None, m=30, max_iter=3000, tol=1e-10, hist_cap=None):
+    """The host GMRES without a preconditioner restated (src/gmres.cu:721-850)."""
+    A = csr(A)
+    x = np.zeros(A.n) if x0 is None else np.array(x0, np.float64, copy=True)
+    cap = hist_cap or (max_iter + max_iter // max(m, 1) + 8)
+    hist = np.zeros(cap)
+    mi, tl, hl, inner = ctypes.c_int(max_iter), ctypes.c_double(tol), ctypes.c_int(), ctypes.c_int()
+    ret = lib().orc_gmres_plain(A.n, A.rp, A.ci, A.v, np.ascontiguousarray(b, np.float64), x, int(m),
                                 ctypes.byref(mi), ctypes.byref(tl), hist, cap,
                                 ctypes.byref(hl), ctypes.byref(inner))
     return _gmres_out(ret, x, mi, tl, hist, hl, inner)

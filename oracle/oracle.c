@@ -638,7 +638,9 @@ static void hist_push(hist_t *h, double v)
 }
 
 /* Operator abstraction so GMRES_leftILU0 and GMRESilu share one restated loop.
- * kind 0 = left ILU (M^-1 = (LU)^-1), kind 1 = split PG. */
+ * kind 0 = left ILU (M^-1 = (LU)^-1), kind 1 = split PG, kind 2 = none: the
+ * host GMRES without a preconditioner (src/gmres.cu:721-850), the same loop on
+ * b, b - A x and A v[i] themselves. */
 typedef struct {
     int kind;
     int n;
@@ -676,19 +678,19 @@ static int gmres_core(const op_t *op, const double *b, double *x, int m,
     /* normb = ||M b||  (left: :593-594 ; split: HostPrecond_rhs :2096-2098) */
     if (op->kind == 0)
         orc_lusolve(n, op->l_rp, op->l_ci, op->l_v, op->u_rp, op->u_ci, op->u_v, b, bb);
-    else
+    else if (op->kind == 1)
         orc_split_left(op->sp, b, bb);
-    double normb = norm2(bb, n);
+    double normb = norm2(op->kind == 2 ? b : bb, n);     /* none: norm2(b) :741 */
     if (normb == 0.0) normb = 1.0;
 
     if (op->kind == 1) {
         orc_split_start(op->sp, x, y);   /* :2102 */
         acc = y;
     }
-    orc_residual(n, op->rp, op->ci, op->v, x, b, rr);
+    orc_residual(n, op->rp, op->ci, op->v, x, b, op->kind == 2 ? r : rr);   /* none :744 */
     if (op->kind == 0)
         orc_lusolve(n, op->l_rp, op->l_ci, op->l_v, op->u_rp, op->u_ci, op->u_v, rr, r);
-    else
+    else if (op->kind == 1)
         orc_split_left(op->sp, rr, r);
     double beta = norm2(r, n);
     resid = beta / normb;
@@ -712,6 +714,8 @@ static int gmres_core(const op_t *op, const double *b, double *x, int m,
                 orc_spmv(n, op->rp, op->ci, op->v, vi, ww);              /* :635 */
                 orc_lusolve(n, op->l_rp, op->l_ci, op->l_v, op->u_rp, op->u_ci,
                             op->u_v, ww, w);                           /* :636 */
+            } else if (op->kind == 2) {
+                orc_spmv(n, op->rp, op->ci, op->v, vi, w);               /* :776 */
             } else {
                 orc_split_right(op->sp, vi, w);                        /* :2143 */
                 orc_spmv(n, op->rp, op->ci, op->v, w, ww);             /* :2144 */
@@ -773,10 +777,10 @@ static int gmres_core(const op_t *op, const double *b, double *x, int m,
          * column i-1 (deliberate fix, as ILU++ does). */
         update(acc, i - 1, H, m, s, V, n);
         if (op->kind == 1) orc_split_right(op->sp, y, x);
-        orc_residual(n, op->rp, op->ci, op->v, x, b, rr);
+        orc_residual(n, op->rp, op->ci, op->v, x, b, op->kind == 2 ? r : rr);   /* none :818 */
         if (op->kind == 0)
             orc_lusolve(n, op->l_rp, op->l_ci, op->l_v, op->u_rp, op->u_ci, op->u_v, rr, r);
-        else
+        else if (op->kind == 1)
             orc_split_left(op->sp, rr, r);
         beta = norm2(r, n);
         resid = beta / normb;
@@ -814,6 +818,14 @@ int orc_gmres_split(int n, const int *rp, const int *ci, const double *v,
                     double *hist, int hist_cap, int *hist_len, int *inner_iters)
 {
     op_t op = {1, n, rp, ci, v, NULL, NULL, NULL, NULL, NULL, NULL, p};
+    return gmres_core(&op, b, x, m, max_iter, tol, hist, hist_cap, hist_len, inner_iters);
+}
+
+int orc_gmres_plain(int n, const int *rp, const int *ci, const double *v,
+                    const double *b, double *x, int m, int *max_iter, double *tol,
+                    double *hist, int hist_cap, int *hist_len, int *inner_iters)
+{
+    op_t op = {2, n, rp, ci, v, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
     return gmres_core(&op, b, x, m, max_iter, tol, hist, hist_cap, hist_len, inner_iters);
 }
 

@@ -111,6 +111,12 @@ int orc_gmres_split(int n, const int *rp, const int *ci, const double *v,
                     const double *b, double *x, int m, int *max_iter, double *tol,
                     double *hist, int hist_cap, int *hist_len, int *inner_iters);
 
+/* The host GMRES without a preconditioner (src/gmres.cu:721-850): the same
+ * loop on b, b - A x and A v[i] themselves. */
+int orc_gmres_plain(int n, const int *rp, const int *ci, const double *v,
+                    const double *b, double *x, int m, int *max_iter, double *tol,
+                    double *hist, int hist_cap, int *hist_len, int *inner_iters);
+
 /* Transient step (src/mna_solve_gpu_gmres.cpp:564-647).  PULSE value of a
  * source at time index it (gen_PULSEut_kernel, src/kernels.cu:223-245);
  * q = {vlo, vhi, td, tr, tf, tw, tp}. */

@@ -1,9 +1,13 @@
 """ctypes binding of oracle/_ref/libgg_ref.so: the reference's own host routines
-(src/SpMV_compute.cpp, src/iluk.cpp, src/itsol.cpp, src/formatConvert.cpp built
-by oracle/Makefile with float = double) behind oracle/ref_shim.cpp.
+(src/SpMV_compute.cpp, src/iluk.cpp, src/itsol.cpp, src/formatConvert.cpp, and
+the host GMRES engines cut out of src/gmres.cu and src/preconditioner.cu by
+oracle/slice_ref.py, built by oracle/Makefile with float = double) behind
+oracle/ref_shim.cpp.
 
-TEST INFRASTRUCTURE ONLY: tests/golden/make_ref_pins.py records what these
-routines compute, tests/test_ref_pins.py reruns them where the library exists.
+TEST INFRASTRUCTURE ONLY: tests/golden/make_ref_pins.py and
+make_ref_engine_pins.py record what these routines compute,
+tests/test_ref_pins.py and test_ref_engine_pins.py rerun them where the
+library exists.
 Never imported by the product package, smoke() or bench.py.
 """
 import ctypes
@@ -16,6 +20,9 @@ _DIR = os.path.join(_HERE, "_ref")
 _LIB = os.path.join(_DIR, "libgg_ref.so")
 _HASHES = os.path.join(_DIR, "sources.sha256")
 _lib = None
+# the files the engines are cut from; every other name in sources.sha256 is
+# compiled whole (the routines of tests/golden/ref_pins.npz)
+ENGINE_FILES = ("gmres.cu", "preconditioner.cu")
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
@@ -27,15 +34,22 @@ def available():
     return os.path.exists(_LIB) and os.path.exists(_HASHES)
 
 
-def source_hashes():
-    """{file name: sha256} of the reference files the library was compiled from"""
+def source_hashes(engines=False):
+    """{file name: sha256} of the reference files the library was compiled
+    from: the files compiled whole, with engines=True also ENGINE_FILES"""
     out = {}
     with open(_HASHES) as f:
         for line in f:
             if line.strip():
                 digest, name = line.split()
-                out[name] = digest
+                if engines or name not in ENGINE_FILES:
+                    out[name] = digest
     return out
+
+
+def engines_available():
+    """the library holds the host GMRES engines (built with the slice)"""
+    return available() and hasattr(lib(), "ref_split_apply")
 
 
 def lib():
@@ -56,6 +70,15 @@ def lib():
         for f in (L.ref_ldcsc2csr, L.ref_ldcsc2csr_double):
             f.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_long, _i64p, _i64p, _f64p,
                           _i32p, _i32p, _f64p]
+        if hasattr(L, "ref_split_apply"):
+            tail = [_f64p, _f64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+            mat = [ctypes.c_int, _i32p, _i32p, _f64p]
+            tri = [_i32p, _i32p, _f64p]
+            L.ref_gmres_left_ilu0.argtypes = mat + tri + tri + tail
+            L.ref_gmres_plain.argtypes = mat + tail
+            L.ref_gmres_split.argtypes = mat + tri + tri + [_f64p, _i32p, _i32p, _f64p, _f64p] + tail
+            L.ref_split_apply.argtypes = ([ctypes.c_int, ctypes.c_int] + tri + tri +
+                                          [_f64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p])
         _lib = L
     return _lib
 
@@ -155,3 +178,46 @@ def ldcsc2csr(m, n, p, i, x):
 def ldcsc2csr_double(m, n, p, i, x):
     """LDcsc2csrMySpMatrixDouble (src/formatConvert.cpp:368-398) -> (row_ptr, col, val)"""
     return _csc(lib().ref_ldcsc2csr_double, m, n, p, i, x)
+
+
+def _engine(fn, args, b, x0, n, m, max_iter, tol):
+    x = np.zeros(n) if x0 is None else np.array(x0, np.float64, copy=True)
+    mi, tl = ctypes.c_int(int(max_iter)), ctypes.c_double(float(tol))
+    ret = fn(*args, np.ascontiguousarray(b, np.float64), x, int(m), ctypes.byref(mi), ctypes.byref(tl))
+    return dict(ret=int(ret), x=x, iters=mi.value, relres=tl.value)
+
+
+def gmres_left_ilu0(A, L, U, b, x0=None, m=30, max_iter=3000, tol=1e-10):
+    """GMRES_leftILU0 (src/gmres.cu:566-717) -> dict(ret, x, iters = *max_iter,
+    relres = *tol as the engine left them)"""
+    A = _csr(A)
+    return _engine(lib().ref_gmres_left_ilu0, (A.n, A.rp, A.ci, A.v, L.rp, L.ci, L.v, U.rp, U.ci, U.v),
+                   b, x0, A.n, m, max_iter, tol)
+
+
+def gmres_plain(A, b, x0=None, m=30, max_iter=3000, tol=1e-10):
+    """the host GMRES without a preconditioner (src/gmres.cu:721-850)"""
+    A = _csr(A)
+    return _engine(lib().ref_gmres_plain, (A.n, A.rp, A.ci, A.v), b, x0, A.n, m, max_iter, tol)
+
+
+def gmres_split(A, P, b, x0=None, m=32, max_iter=10000, tol=1e-7):
+    """GMRESilu (src/gmres.cu:2069-2252) over MyILUPP::HostPrecond_rhs /
+    _starting_value / _left / _right (src/preconditioner.cu:1055-1137);
+    P: an oracle.Split (its arrays are only read)"""
+    A = _csr(A)
+    return _engine(lib().ref_gmres_split,
+                   (A.n, A.rp, A.ci, A.v, P.L.rp, P.L.ci, P.L.v, P.U.rp, P.U.ci, P.U.v, P.middle,
+                    P.perm_row, P.perm_col, P.lscale, P.rscale), b, x0, A.n, m, max_iter, tol)
+
+
+SPLIT_MAPS = ("left", "right", "start", "rhs")
+
+
+def split_apply(P, which, v):
+    """MyILUPP::HostPrecond_left / _right / _starting_value / _rhs
+    (src/preconditioner.cu:1055-1137) on v; which: a name in SPLIT_MAPS"""
+    out = np.zeros(P.L.n)
+    lib().ref_split_apply(SPLIT_MAPS.index(which), P.L.n, P.L.rp, P.L.ci, P.L.v, P.U.rp, P.U.ci, P.U.v, P.middle,
+                          P.perm_row, P.perm_col, P.lscale, P.rscale, np.ascontiguousarray(v, np.float64), out)
+    return out

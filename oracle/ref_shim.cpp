@@ -4,7 +4,9 @@
  * TEST INFRASTRUCTURE ONLY.  oracle/Makefile links this file with the
  * reference's src/SpMV_compute.cpp, src/iluk.cpp, src/itsol.cpp and
  * src/formatConvert.cpp (compiled from the reference checkout, never copied
- * here) into _ref/libgg_ref.so; oracle/ref.py loads it.  Everything is built
+ * here) and with the host GMRES engines slice_ref.py cuts out of src/gmres.cu
+ * and src/preconditioner.cu (at the end of this file) into
+ * _ref/libgg_ref.so; oracle/ref.py loads it.  Everything is built
  * with ref_widen.h in front, so the reference's `float` is double here and in
  * the declarations below.  No arithmetic happens in this file: it only moves
  * arrays into and out of the reference's own structures.
@@ -165,3 +167,119 @@ void ref_ldcsc2csr_double(long nzmax, long m, long n, long *p, long *i, double *
 }
 
 }  // extern "C"
+
+#ifdef GG_REF_ENGINES
+/*
+ * The reference's host GMRES engines.  src/gmres.cu and src/preconditioner.cu
+ * need cusp, cublas and <<<>>> and do not compile as files; slice_ref.py cuts
+ * the plain C++ functions out of them into _ref/gmres_host_slice.cpp (the
+ * vector helpers, Update, the two plane-rotation routines, GMRES_leftILU0, the
+ * unpreconditioned GMRES, GMRESilu and MyILUPP::HostPrecond_rhs /
+ * _starting_value / _left / _right), which is included below.  GMRESilu takes
+ * a Preconditioner &: this project's compat header has the reference's layout.
+ * MyILUPP is declared here with exactly the members the four routines read;
+ * the reference's own class drags in cusparse.
+ */
+#include "../include/compat/preconditioner.h"
+
+class MyILUPP : public Preconditioner {
+public:
+    IndexType *l_rowIndices, *l_indices;
+    IndexType *u_rowIndices, *u_indices;
+    double *l_val_double, *u_val_double;
+    ValueType *middle_val;
+    IndexType *permRow_indices, *permCol_indices;
+    double *lscale_val, *rscale_val;
+    float *tmpvector;
+
+    /* never reached by GMRESilu */
+    void HostPrecond(const ValueType *, ValueType *) { abort(); }
+    void DevPrecond(const ValueType *, ValueType *) { abort(); }
+    void Initilize(const MySpMatrix &) { abort(); }
+    void DevPrecond_rhs(float *, float *) { abort(); }
+    void DevPrecond_right(float *, float *) { abort(); }
+    void DevPrecond_left(float *, float *) { abort(); }
+    void DevPrecond_starting_value(float *, float *) { abort(); }
+
+    /* defined by the slice */
+    void HostPrecond_rhs(const ValueType *i_data, ValueType *o_data);
+    void HostPrecond_right(const ValueType *i_data, ValueType *o_data);
+    void HostPrecond_left(const ValueType *i_data, ValueType *o_data);
+    void HostPrecond_starting_value(const ValueType *i_data, ValueType *o_data);
+};
+
+#include "_ref/gmres_host_slice.cpp"
+
+namespace {
+/* GMRES_leftILU0 and GMRES write a line to cout per iteration */
+struct QuietCout {
+    std::streambuf *old;
+    QuietCout() : old(std::cout.rdbuf(NULL)) {}
+    ~QuietCout() { std::cout.rdbuf(old); }
+};
+
+void fill_ilupp(MyILUPP &P, int n, int *l_rp, int *l_ci, double *l_v, int *u_rp, int *u_ci, double *u_v,
+                double *middle, int *perm_row, int *perm_col, double *lscale, double *rscale)
+{
+    P.numRows = n;
+    P.l_rowIndices = l_rp; P.l_indices = l_ci; P.l_val_double = l_v;
+    P.u_rowIndices = u_rp; P.u_indices = u_ci; P.u_val_double = u_v;
+    P.middle_val = middle;
+    P.permRow_indices = perm_row; P.permCol_indices = perm_col;
+    P.lscale_val = lscale; P.rscale_val = rscale;
+    P.tmpvector = (float *)malloc(sizeof(float) * (n > 0 ? n : 1));
+}
+}  // namespace
+
+extern "C" {
+
+int ref_has_engines(void) { return 1; }
+
+/* Each engine returns its ret and leaves x, *max_iter and *tol as it left them. */
+int ref_gmres_left_ilu0(int n, const int *rp, const int *ci, const double *v,
+                        const int *l_rp, const int *l_ci, const double *l_v,
+                        const int *u_rp, const int *u_ci, const double *u_v,
+                        const double *b, double *x, int m, int *max_iter, double *tol)
+{
+    QuietCout q;
+    return GMRES_leftILU0(v, rp, ci, x, b, n, m, max_iter, tol, l_v, l_rp, l_ci, u_v, u_rp, u_ci);
+}
+
+int ref_gmres_plain(int n, const int *rp, const int *ci, const double *v,
+                    const double *b, double *x, int m, int *max_iter, double *tol)
+{
+    QuietCout q;
+    return GMRES(v, rp, ci, x, b, n, m, max_iter, tol);
+}
+
+int ref_gmres_split(int n, const int *rp, const int *ci, const double *v,
+                    int *l_rp, int *l_ci, double *l_v, int *u_rp, int *u_ci, double *u_v,
+                    double *middle, int *perm_row, int *perm_col, double *lscale, double *rscale,
+                    const double *b, double *x, int m, int *max_iter, double *tol)
+{
+    QuietCout q;
+    MyILUPP P;
+    fill_ilupp(P, n, l_rp, l_ci, l_v, u_rp, u_ci, u_v, middle, perm_row, perm_col, lscale, rscale);
+    int ret = GMRESilu(v, rp, ci, x, b, n, m, max_iter, tol, P);
+    free(P.tmpvector);
+    return ret;
+}
+
+/* one of MyILUPP's four host maps on its own: which = 0 HostPrecond_left,
+ * 1 _right, 2 _starting_value, 3 _rhs */
+void ref_split_apply(int which, int n,
+                     int *l_rp, int *l_ci, double *l_v, int *u_rp, int *u_ci, double *u_v,
+                     double *middle, int *perm_row, int *perm_col, double *lscale, double *rscale,
+                     const double *in, double *out)
+{
+    MyILUPP P;
+    fill_ilupp(P, n, l_rp, l_ci, l_v, u_rp, u_ci, u_v, middle, perm_row, perm_col, lscale, rscale);
+    if (which == 0) P.HostPrecond_left(in, out);
+    else if (which == 1) P.HostPrecond_right(in, out);
+    else if (which == 2) P.HostPrecond_starting_value(in, out);
+    else P.HostPrecond_rhs(in, out);
+    free(P.tmpvector);
+}
+
+}  // extern "C"
+#endif /* GG_REF_ENGINES */

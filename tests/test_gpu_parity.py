@@ -815,6 +815,61 @@ def test_transient_mixed_sources(solver):
     solver.set_taps([])
 
 
+def test_transient_source_edges(solver):
+    """The source-waveform kernels where their branches meet: a PULSE whose
+    period divides the step times (t - floor(t / tp) * tp lands on 0), PULSEs
+    with tr = 0 and with tf = 0 (no division by them is reached), a PULSE
+    whose td, td + tr, td + tr + tw fall on step times, PWLs with a breakpoint
+    on a step time, with the last point before the run ends, with one point,
+    with the first point at t = 0 and before it (every t0 <= 0: before t0 the
+    reference reads out of bounds and the value deliberately holds v0).
+    12 steps on the 40 x 40 grid, bit-identical to the order-matched step
+    driver as test_transient_mixed_sources."""
+    nx, ny = 40, 40
+    h = 1e-2
+    nsteps = 12
+    A = M.transient(M.laplacian_5pt(nx, ny), c=1e-3, h=h)
+    n = A.shape[0]
+    cdiag = np.full(n, 1e-3 / h)
+    srcs = [
+        (O.SRC_PULSE, [0.0, 2e-3, h, h, h, h, 4 * h]),                  # three whole periods
+        (O.SRC_PULSE, [1e-4, 2e-3, 2 * h, 0.0, 2 * h, 3 * h, 20 * h]),  # tr = 0
+        (O.SRC_PULSE, [1e-4, 2e-3, 2 * h, 2 * h, 0.0, 3 * h, 20 * h]),  # tf = 0
+        (O.SRC_PULSE, [0.0, -1.5e-3, 2 * h, 3 * h, 2 * h, 4 * h, 20 * h]),  # breakpoints at steps 2, 5, 9, 11
+        (O.SRC_PWL, [0.0, 0.0, 3 * h, 1e-3, 6 * h, -5e-4, 20 * h, 0.0]),    # breakpoints at steps 3 and 6
+        (O.SRC_PWL, [0.0, 0.0, 2 * h, 1e-3, 5 * h, 2e-3]),              # ends at step 5
+        (O.SRC_PWL, [0.0, 7e-4]),                                       # one point
+        (O.SRC_PWL, [0.0, 1e-3, 4.5 * h, 0.0]),                         # first point at t = 0
+        (O.SRC_PWL, [-h, 5e-4, 3.5 * h, 1e-3, 8 * h, 0.0]),             # first point before t = 0
+    ]
+    nodes = np.sort(np.random.default_rng(22).choice(n, size=len(srcs), replace=False)).astype(np.int32)
+    # the waveforms do pass through the edges they are there for
+    val = lambda k, it: O.source_value(srcs[k][0], srcs[k][1], it, h)
+    # (the reduced time of steps 5, 6, 7 is a rounding error away from a breakpoint: 3.5e-19 at step 5)
+    assert [val(0, it) for it in (4, 8, 12)] == [0.0] * 3 and val(0, 2) == val(0, 10) == 2e-3
+    assert 0.0 < val(0, 5) < 1e-18 and val(0, 6) == pytest.approx(2e-3, rel=1e-12) and val(0, 6) != 2e-3
+    assert val(1, 1) == 1e-4 and val(1, 2) == 2e-3 and val(2, 7) == 1e-4
+    assert val(3, 2) == 0.0 and val(3, 5) == val(3, 8) == -1.5e-3 and val(3, 11) == 0.0
+    assert val(4, 3) == 1e-3 and val(4, 6) == -5e-4
+    assert val(5, 5) == val(5, 12) == 2e-3 and [val(6, it) for it in (1, 12)] == [7e-4] * 2
+    assert 0.0 < val(7, 4) < val(7, 1) < 1e-3 and val(7, 5) == 0.0 and 5e-4 < val(8, 1) < 1e-3
+    assert all(np.isfinite(val(k, it)) for k in range(len(srcs)) for it in range(1, nsteps + 1))
+    ports = np.concatenate([nodes, [n - 1]]).astype(np.int32)
+    x0 = np.zeros(n)
+    L, U = O.ilu0(A)
+    run = lambda: O.transient(A, L, U, nsteps, h, cdiag, nodes, None, ports, x0, m=32, max_iter=10000,
+                              tol=1e-7, sources=srcs)
+    o, ot = oracle_both(run, n, nx=nx)
+    solver.set_matrix(A)
+    solver.set_precond_ilu0()
+    assert solver.uses_wavefront
+    g = solver.transient_src(nsteps, h, cdiag, nodes, srcs, ports, x0, restart=32, max_iter=10000, tol=1e-7)
+    assert g["iters_total"] == ot["iters_total"] == o["iters_total"]
+    assert np.array_equal(g["ports"], ot["ports"]) and np.array_equal(g["x"], ot["x"])
+    assert rel_err(g["x"], o["x"]) <= 1e-10
+    assert np.all(np.max(np.abs(ot["ports"][:len(srcs)]), axis=1) > 0)     # every source drove its node
+
+
 @pytest.mark.gpu
 def test_profile_kind_mask():
     """gg_profile_enable(kinds): only the selected families are bracketed."""
