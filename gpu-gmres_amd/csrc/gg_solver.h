@@ -81,6 +81,7 @@ void pipe_release(gg_solver *s);            // gg_destroy
 // the Ppad-long work vectors, partials, control block, error word; bicgstab: also the
 // three vectors that solve alone keeps (bi_rt, bi_t, bi_q)
 void ensure_vectors(gg_solver *s, bool bicgstab = false);
+void zero_vectors(gg_solver *s);            // those vectors back to +0, padding included
 void apply_minv(gg_solver *s, Gate g, const double *in, double *out, int i = -1);   // out = M in
 void reset_wave(DevTri *T, hipStream_t st);
 void check_err(gg_solver *s);

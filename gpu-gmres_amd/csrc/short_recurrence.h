@@ -95,6 +95,9 @@ int solve_short_recurrence(gg_solver *s, const double *d_b, double *d_x, const g
     else if (h.done & SR_BREAKDOWN) {
         ret = GG_EBREAKDOWN;
         set_error(M::breakdown(h));
+        // the scalar may not have been finite: NaN in the vectors' padding would
+        // reach every dot of the next solve on this solver
+        zero_vectors(s);
     }
     if (res) {
         res->status = ret;

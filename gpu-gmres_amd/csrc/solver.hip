@@ -777,6 +777,17 @@ void gg::ensure_vectors(gg_solver *s, bool bicgstab)
     s->vec_ok = true;
 }
 
+// Every kernel keeps the padding slots of a work vector at +0 (0 * finite + 0),
+// and every dot sums them.  A scalar that is not finite breaks that: alpha = NaN
+// or inf leaves NaN * 0 in the padding, which no later solve overwrites.  The
+// short-recurrence solves call this after a breakdown (x has left by then).
+void gg::zero_vectors(gg_solver *s)
+{
+    for (DBuf<double> *b : {&s->w, &s->ww, &s->r, &s->rr, &s->bb, &s->t1, &s->t2, &s->z, &s->xv, &s->bv, &s->y,
+                            &s->bi_rt, &s->bi_t, &s->bi_q})
+        if (b->p) GG_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), s->st));
+}
+
 namespace {
 
 void ensure_workspace(gg_solver *s, int m)

@@ -32,36 +32,46 @@ def _bad(v):
     return not math.isfinite(v) or v == 0.0
 
 
-def bicgstab(A, minv, b, x0=None, max_iter=3000, tol=1e-10, dot=None):
+def bicgstab(A, minv, b, x0=None, max_iter=3000, tol=1e-10, dot=None, info=None):
     """(ret, x, iters, relres, hist): ret 0 converged, 1 max_iter exhausted,
-    BREAKDOWN; hist = [res0, res after each iteration]; x the last iterate"""
+    BREAKDOWN; hist = [res0, res after each iteration]; x the last iterate.
+    info: a dict that receives the exit taken -- info["why"] one of "conv0",
+    "conv", "exhausted", "rho0" (rho at the start), "rtv", "omega", "rho"
+    (omega named first when both are bad, as k_bi_p does), and info["bad"] the
+    offending scalar (None where nothing broke down)"""
     if dot is None:
         dot = lambda u, v: float(np.dot(u, v))      # noqa: E731
+
+    def out(ret, why, bad=None):
+        if info is not None:
+            info["why"] = why
+            info["bad"] = bad
+        return ret, x, it, res, np.array(hist)
     A = O.csr(A)
     b = np.asarray(b, np.float64)
     x = np.zeros(A.n) if x0 is None else np.array(x0, np.float64, copy=True)
-    bb = minv(b)
-    normb = math.sqrt(dot(bb, bb))
-    if normb == 0.0:
-        normb = 1.0
-    r = minv(O.residual(A, x, b))
-    rr = dot(r, r)
-    res = math.sqrt(rr) / normb if rr >= 0.0 else float("nan")
-    hist = [res]
-    if res <= tol:
-        return 0, x, 0, res, np.array(hist)
-    rt = r.copy()
-    rho = dot(rt, r)
-    if _bad(rho):
-        return BREAKDOWN, x, 0, res, np.array(hist)
-    p = r.copy()
     it = 0
     with np.errstate(over="ignore", invalid="ignore"):
+        bb = minv(b)
+        normb = math.sqrt(dot(bb, bb))
+        if normb == 0.0:
+            normb = 1.0
+        r = minv(O.residual(A, x, b))
+        rr = dot(r, r)
+        res = math.sqrt(rr) / normb if rr >= 0.0 else float("nan")
+        hist = [res]
+        if res <= tol:
+            return out(0, "conv0")
+        rt = r.copy()
+        rho = dot(rt, r)
+        if _bad(rho):
+            return out(BREAKDOWN, "rho0", rho)
+        p = r.copy()
         while it < max_iter:
             v = minv(O.spmv(A, p))
             rtv = dot(rt, v)
             if _bad(rtv):
-                return BREAKDOWN, x, it, res, np.array(hist)
+                return out(BREAKDOWN, "rtv", rtv)
             alpha = rho / rtv
             s = (-alpha) * v + r
             t = minv(O.spmv(A, s))
@@ -76,10 +86,12 @@ def bicgstab(A, minv, b, x0=None, max_iter=3000, tol=1e-10, dot=None):
             it += 1
             hist.append(res)
             if res < tol:
-                return 0, x, it, res, np.array(hist)
-            if _bad(omega) or _bad(rhon):
-                return BREAKDOWN, x, it, res, np.array(hist)
+                return out(0, "conv")
+            if _bad(omega):
+                return out(BREAKDOWN, "omega", omega)
+            if _bad(rhon):
+                return out(BREAKDOWN, "rho", rhon)
             beta = (rhon / rho) * (alpha / omega)
             p = beta * ((-omega) * v + p) + r
             rho = rhon
-    return 1, x, it, res, np.array(hist)
+    return out(1, "exhausted")

@@ -60,48 +60,59 @@ def layout_dot(lay2nat, G):
     return dot
 
 
-def pcg(A, minv, b, x0=None, max_iter=3000, tol=1e-10, dot=None):
+def pcg(A, minv, b, x0=None, max_iter=3000, tol=1e-10, dot=None, info=None):
     """(ret, x, iters, relres, hist): ret 0 converged, 1 max_iter exhausted,
-    BREAKDOWN; hist = [res0, res after each iteration]; x the last iterate"""
+    BREAKDOWN; hist = [res0, res after each iteration]; x the last iterate.
+    info: a dict that receives the exit taken -- info["why"] one of "conv0",
+    "conv", "exhausted", "rz0" (r.z not > 0 at the start), "pq", "rz", and
+    info["bad"] the offending scalar (None where nothing broke down)"""
     if dot is None:
         dot = lambda u, v: float(np.dot(u, v))      # noqa: E731
+
+    def out(ret, why, bad=None):
+        if info is not None:
+            info["why"] = why
+            info["bad"] = bad
+        return ret, x, it, res, np.array(hist)
     A = O.csr(A)
     b = np.asarray(b, np.float64)
     x = np.zeros(A.n) if x0 is None else np.array(x0, np.float64, copy=True)
-    bb = minv(b)
-    normb = math.sqrt(dot(bb, bb))
-    if normb == 0.0:
-        normb = 1.0
-    r = O.residual(A, x, b)
-    z = minv(r)
-    res = math.sqrt(dot(z, z)) / normb
-    hist = [res]
-    rz = dot(r, z)
-    if res <= tol:
-        return 0, x, 0, res, np.array(hist)
-    if not rz > 0.0:
-        return BREAKDOWN, x, 0, res, np.array(hist)
-    p = z.copy()
     it = 0
-    while it < max_iter:
-        q = O.spmv(A, p)
-        pq = dot(p, q)
-        if not pq > 0.0:
-            return BREAKDOWN, x, it, res, np.array(hist)
-        alpha = rz / pq
-        x = alpha * p + x
-        r = (-alpha) * q + r
+    with np.errstate(over="ignore", invalid="ignore"):
+        bb = minv(b)
+        normb = math.sqrt(dot(bb, bb))
+        if normb == 0.0:
+            normb = 1.0
+        r = O.residual(A, x, b)
         z = minv(r)
-        rzn = dot(r, z)
         zz = dot(z, z)
         res = math.sqrt(zz) / normb if zz >= 0.0 else float("nan")
-        it += 1
-        hist.append(res)
-        if res < tol:
-            return 0, x, it, res, np.array(hist)
-        if not rzn > 0.0:
-            return BREAKDOWN, x, it, res, np.array(hist)
-        beta = rzn / rz
-        p = beta * p + z
-        rz = rzn
-    return 1, x, it, res, np.array(hist)
+        hist = [res]
+        rz = dot(r, z)
+        if res <= tol:
+            return out(0, "conv0")
+        if not rz > 0.0:
+            return out(BREAKDOWN, "rz0", rz)
+        p = z.copy()
+        while it < max_iter:
+            q = O.spmv(A, p)
+            pq = dot(p, q)
+            if not pq > 0.0:
+                return out(BREAKDOWN, "pq", pq)
+            alpha = rz / pq
+            x = alpha * p + x
+            r = (-alpha) * q + r
+            z = minv(r)
+            rzn = dot(r, z)
+            zz = dot(z, z)
+            res = math.sqrt(zz) / normb if zz >= 0.0 else float("nan")
+            it += 1
+            hist.append(res)
+            if res < tol:
+                return out(0, "conv")
+            if not rzn > 0.0:
+                return out(BREAKDOWN, "rz", rzn)
+            beta = rzn / rz
+            p = beta * p + z
+            rz = rzn
+    return out(1, "exhausted")

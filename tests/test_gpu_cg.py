@@ -194,6 +194,9 @@ def test_cg_launches_past_convergence_change_nothing():
 
 
 def test_cg_breakdown_on_a_negative_definite_matrix():
+    """ILU(0) of a negative definite matrix is negative definite: r.z = r.Mr < 0
+    at the start, so the solve ends in k_cg_p<START> before k_cg_xr runs
+    (tests/sr_exit_cases.py `rz0`; `pq0` there is the p.Ap exit at iteration 0)"""
     s = make("negative", "ilu0")
     try:
         o = reference(s, "negative", "ilu0")
@@ -289,6 +292,48 @@ def test_cg_transient_matches_solve_loop():
             x = g["x"]
             assert np.array_equal(r["ports"][:, it], x[ports])
         assert r["ret"] == 0 and np.array_equal(r["x"], x) and r["iters_total"] == total > 0
+    finally:
+        s.close()
+
+
+def test_cg_transient_with_breaking_steps():
+    """an indefinite matrix (16 x 17 shifted by -0.3 I, ILU0): the sources are
+    still off in step 1 (b = 0: converged at the start), then p.Ap turns
+    negative in every step (with cg_ref.pcg's plain dots after 1, 1 and 0
+    iterations).  Every step of the device loop is still the solve gg_solve
+    runs on the step's right-hand side, warm-started from the last iterate the
+    step before left, and the loop returns the last step's status"""
+    h = 1e-2
+    A = (sp.csr_matrix(M.laplacian_5pt(16, 17)) - 0.3 * sp.identity(272, format="csr")).tocsr()
+    A.sort_indices()
+    n = A.shape[0]
+    cdiag = np.full(n, 1e-3 / h)
+    nodes = np.array([3, 40, 200], np.int32)
+    pulses = np.array([[0.0, 1.0, h, 2e-2, 2e-2, 5e-2, 0.2]] * 3)       # delayed by one step
+    ports = np.array([0, n - 1], np.int32)
+    s = ggmres.Solver(0)
+    try:
+        s.set_matrix(A)
+        s.set_precond_ilu0()
+        r = s.transient(4, h, cdiag, nodes, pulses, ports, np.zeros(n), restart=30, max_iter=3000, tol=1e-10,
+                        flags=CG)
+        x = np.zeros(n)
+        total = 0
+        rets = []
+        for it in range(1, 5):
+            u = np.array([O.pulse(q, it, h) for q in pulses])
+            w = O.transient_rhs(cdiag, nodes, u, x)
+            g = s.solve(w, x0=x, restart=30, max_iter=3000, tol=1e-10, flags=CG)
+            assert g["restarts"] == 0
+            rets.append((g["ret"], g["iters"]))
+            total += g["iters"]
+            x = g["x"]
+            assert np.array_equal(r["ports"][:, it], x[ports]), it
+        print(f"steps (ret, iters): {rets}")
+        assert rets[0] == (0, 0) and all(ret == ggmres.EBREAKDOWN for ret, _ in rets[1:])
+        assert r["ret"] == rets[-1][0] == ggmres.EBREAKDOWN == -8
+        assert np.all(np.isfinite(x)) and np.any(x)
+        assert np.array_equal(r["x"], x) and r["iters_total"] == total > 0
     finally:
         s.close()
 

@@ -172,8 +172,10 @@ def test_cg_batch_smallest_layout():
 
 
 def test_cg_batch_breakdown_stays_in_its_scenario():
-    """a negative definite matrix: p.Ap < 0 at iteration 0 for every nonzero
-    right-hand side; the zero one converges at the start"""
+    """a negative definite matrix with ILU(0), itself negative definite: r.z =
+    r.Mr < 0 at the start for every nonzero right-hand side (k_cg_p<START>'s
+    exit, tests/sr_exit_cases.py `rz0`; k_cg_xr never runs); the zero one
+    converges at the start"""
     import scipy.sparse as sp
     A = -sp.csr_matrix(M.laplacian_5pt(16, 17))
     A.sort_indices()
@@ -198,6 +200,93 @@ def test_cg_batch_breakdown_stays_in_its_scenario():
         # still usable: the zero right-hand side alone converges at the start
         z = s.solve_cg_batch(B[1:2], X0[1:2])
         assert z["ret"] == 0 and z["iters"] == [0]
+    finally:
+        s.close()
+
+
+def indefinite_case():
+    """60 x 52 shifted by -0.02 I (indefinite), ILU(0): with cg_ref.pcg's plain
+    dots p.Ap turns negative at iterations 5, 10, 9 and 6 (scenarios 0, 1, 3, 5),
+    b = 0 converges at the start (2) and the warm start converges in 9 (4,
+    relres 8.2e-11) -- breakdowns after x and r have moved, at different
+    iterations, while other scenarios go on through the same launches"""
+    import scipy.sparse as sp
+    A = (sp.csr_matrix(M.laplacian_5pt(60, 52)) - 0.02 * sp.identity(60 * 52, format="csr")).tocsr()
+    A.sort_indices()
+    n = A.shape[0]
+    one = A @ np.ones(n)
+    B = np.array([one, np.random.default_rng(1).standard_normal(n), np.zeros(n),
+                  np.random.default_rng(3).standard_normal(n), one, np.random.default_rng(2).standard_normal(n)])
+    X0 = np.zeros((6, n))
+    X0[4] = 1.0 + 1e-8 * np.random.default_rng(9).standard_normal(n)
+    return A, B, X0
+
+
+def broken(ref):
+    """(scenario, iteration) of the lowest scenario of the single solves that broke down"""
+    q = [r["ret"] for r in ref].index(-8)
+    return q, ref[q]["iters"]
+
+
+@pytest.mark.parametrize("path", ["batched", "scenario by scenario"])
+def test_cg_batch_breakdowns_after_iteration_0(path, monkeypatch):
+    """k_cg_xr's exit at several iterations greater than 0 in one batch, beside a
+    scenario that converges and one that converged at the start; with max_iter =
+    8 a mix of -8, 1 and 0 in one launch sequence"""
+    A, B, X0 = indefinite_case()
+    s = make(A)
+    try:
+        assert s.uses_wavefront and s.batch_engine
+        ref = singles(s, B, X0)
+        stat = [(r["ret"], r["iters"]) for r in ref]
+        print(f"single solves: {stat}")
+        # on the single solves alone: breakdowns at three or more distinct iterations
+        # greater than 0, a convergence after iterations, a convergence at the start
+        assert len({k for ret, k in stat if ret == -8 and k > 0}) >= 3
+        assert any(ret == 0 and k > 0 for ret, k in stat) and (0, 0) in stat
+        ref8 = singles(s, B, X0, max_iter=8)
+        stat8 = [(r["ret"], r["iters"]) for r in ref8]
+        print(f"single solves, max_iter 8: {stat8}")
+        assert {ret for ret, _ in stat8} == {-8, 1, 0} and (1, 8) in stat8
+        if path != "batched":
+            monkeypatch.setenv("GG_BATCH_SEQ", "1")      # test_cg_batch_scenario_by_scenario's mechanism
+            assert not s.batch_engine
+        for what, g, r in (("S = 6", s.solve_cg_batch(B, X0), ref),
+                           ("S = 2", s.solve_cg_batch(B[:2], X0[:2]), ref[:2]),
+                           ("S = 6, max_iter 8", s.solve_cg_batch(B, X0, max_iter=8), ref8)):
+            msg = ggmres.lib().gg_last_error().decode()
+            same_as_singles(g, r, f"{path} {what}")
+            q, k = broken(r)
+            assert g["ret"] == ggmres.EBREAKDOWN == -8, what
+            assert f"scenario {q} at iteration {k} " in msg, (what, msg)
+    finally:
+        s.close()
+
+
+def test_cg_batch_pq_breakdown_at_iteration_0():
+    """tests/sr_exit_cases.py `pq0` (negative definite, no preconditioner: r.z =
+    r.r > 0, p.Ap < 0 in the first iteration) through the batch entry: k_cg_xr's
+    exit at iteration 0, scenario by scenario (no batched launches without
+    triangular factors)"""
+    import sr_exit_cases as X
+    c = X.cases()["pq0"]
+    n = c.A.shape[0]
+    B = np.array([c.b, np.zeros(n), np.random.default_rng(6).standard_normal(n)])
+    X0 = np.zeros((3, n))
+    for q, want in enumerate([("pq", 0), ("conv0", 0), ("pq", 0)]):
+        info = {}
+        o = X.reference(c._replace(b=B[q]), info=info)
+        assert (info["why"], o[2]) == want, q
+    s = make(c.A, "none")
+    try:
+        assert not s.batch_engine
+        ref = singles(s, B, X0)
+        g = s.solve_cg_batch(B, X0)
+        msg = ggmres.lib().gg_last_error().decode()
+        assert g["status"] == [-8, 0, -8] and g["iters"] == [0, 0, 0] and g["ret"] == ggmres.EBREAKDOWN
+        assert np.array_equal(g["x"], X0)
+        same_as_singles(g, ref, "pq0")
+        assert "scenario 0 at iteration 0 " in msg
     finally:
         s.close()
 
