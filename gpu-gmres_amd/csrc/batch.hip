@@ -112,6 +112,7 @@ void batch_release(gg_solver *s)
     delete s->batch;
     s->batch = nullptr;
     cg_batch_release(s);
+    bicgstab_batch_release(s);
 }
 
 namespace {
@@ -451,7 +452,7 @@ int solve_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d
     GG_REQUIRE(opt->flags == 0, GG_EINVAL, "gg_solve_batch: no flags are defined for the batch");
     GG_REQUIRE(ldb >= s->A.n && ldx >= s->A.n, GG_EINVAL, "gg_solve_batch: leading dimension below n");
     GG_HIP(hipSetDevice(s->device));
-    s->batch_last_cg = false;
+    s->batch_last = BATCH_GMRES;
     if (!batchable(s)) return solve_batch_seq(s, S, d_b, ldb, d_x, ldx, opt, res);
     for (int attempt = 0;; attempt++) {
         try {
@@ -477,7 +478,7 @@ bool batch_engine_on(gg_solver *s) { return batchable(s); }
 std::string batch_mgs_kernel(gg_solver *s)
 {
     const BatchWs *B = s->batch;
-    if (s->batch_last_cg || !B || B->ran_mgs <= 0) return "";
+    if (s->batch_last != BATCH_GMRES || !B || B->ran_mgs <= 0) return "";
     const int J = arnoldi_persist_units(s->G, s->Ppad);
     if (B->ran_mgs == 2) return "k_arnoldi_persist2<" + std::to_string(J) + ">";
     return arnoldi_persist_name(J);
@@ -485,7 +486,8 @@ std::string batch_mgs_kernel(gg_solver *s)
 
 long long batch_history(gg_solver *s, int q, double *out, long long cap)
 {
-    if (s->batch_last_cg) return cg_batch_history(s, q, out, cap);
+    if (s->batch_last == BATCH_CG) return cg_batch_history(s, q, out, cap);
+    if (s->batch_last == BATCH_BICGSTAB) return bicgstab_batch_history(s, q, out, cap);
     GG_REQUIRE(s->batch, GG_ESTATE, "gg_batch_history: no batched solve holds that scenario");
     return s->batch->arena.history(s->batch->hist, q, out, cap);
 }
@@ -547,16 +549,18 @@ int gg_transient_batch(gg_solver *s, int nrhs, int nsteps, double h, const doubl
                        int *iters_total)
 {
     GG_API_BEGIN
-    return transient_batch(s, false, nrhs, nsteps, h, cdiag, src_off, src_node, src_kind, src_ptr, src_data, nport,
-                           port, x, opt, port_out, iters_total);
+    return transient_batch(s, BATCH_GMRES, nrhs, nsteps, h, cdiag, src_off, src_node, src_kind, src_ptr, src_data,
+                           nport, port, x, opt, port_out, iters_total);
     GG_API_END
 }
 
 }  // extern "C"
 
-// the transient loop of every scenario (gg_transient_batch; cg: gg_transient_cg_batch,
-// the step solved by solve_cg_batch with its first chunk sized by the previous step)
-int gg::transient_batch(gg_solver *s, bool cg, int nrhs, int nsteps, double h, const double *cdiag,
+// the transient loop of every scenario (gg_transient_batch; method BATCH_CG:
+// gg_transient_cg_batch, BATCH_BICGSTAB: gg_transient_bicgstab_batch -- the step
+// solved by solve_cg_batch / solve_bicgstab_batch with its first chunk sized by
+// the previous step)
+int gg::transient_batch(gg_solver *s, BatchMethod method, int nrhs, int nsteps, double h, const double *cdiag,
                         const int *src_off, const int *src_node, const int *src_kind, const int *src_ptr,
                         const double *src_data, int nport, const int *port, double *x, const gg_options *opt,
                         double *port_out, int *iters_total)
@@ -626,12 +630,13 @@ int gg::transient_batch(gg_solver *s, bool cg, int nrhs, int nsteps, double h, c
     for (int it = 1; it <= nsteps; it++) {
         launch_transient_step_b(n, nrhs, maxsrc, d_soff.p, d_kind.p, d_dptr.p, d_data.p, it, h, d_u.p, d_sptr.p,
                                 d_sidx.p, d_c.p, d_x.p, d_w.p, n, st);
-        const int rc = cg ? solve_cg_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data())
-                          : solve_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data());
+        const int rc = method == BATCH_CG         ? solve_cg_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data())
+                       : method == BATCH_BICGSTAB ? solve_bicgstab_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data())
+                                                  : solve_batch(s, nrhs, d_w.p, n, d_x.p, n, opt, res.data());
         if (rc < 0) return rc;
         if (rc) status = rc;
         for (int q = 0; q < nrhs; q++) tot[q] += res[q].iters;
-        if (cg) {
+        if (method != BATCH_GMRES) {
             int mx = 0;
             for (int q = 0; q < nrhs; q++) mx = std::max(mx, res[q].inner_iters);
             s->batch_iter_hint = mx;

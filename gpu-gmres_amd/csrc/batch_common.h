@@ -1,5 +1,5 @@
 // batch_common.h -- what the many-RHS solves share (batch.hip: GMRES,
-// cg_batch.hip: CG): the per-scenario arena, the ring of read-back slots, the
+// cg_batch.hip: CG, bicgstab_batch.hip: BiCGStab): the per-scenario arena, the ring of read-back slots, the
 // triage of the error word, the staging around a solve and the host-array entry
 // point.  A method keeps which arrays a scenario owns, the launches of an
 // iteration or cycle, how a control block becomes a gg_result, and its fallbacks.
@@ -244,7 +244,8 @@ float stage_out(gg_solver *s, const BatchArena &A, ReadRing<State> &ring, const 
     return ms;
 }
 
-// The host-array entry points (gg_solve_batch, gg_solve_cg_batch; name: the
+// The host-array entry points (gg_solve_batch, gg_solve_cg_batch,
+// gg_solve_bicgstab_batch; name: the
 // entry point's, for its messages): upload, the device engine, download.
 // download_on_error: x is copied back whatever the engine returned; otherwise
 // not after a negative code other than GG_EBREAKDOWN.

@@ -263,7 +263,7 @@ int solve_cg_batch(gg_solver *s, int S, const double *d_b, long long ldb, double
                "DIAG, AINV, ILU0, ILUK, LU), not the split or caller-supplied ones");
     GG_REQUIRE(ldb >= s->A.n && ldx >= s->A.n, GG_EINVAL, "gg_solve_cg_batch: leading dimension below n");
     GG_HIP(hipSetDevice(s->device));
-    s->batch_last_cg = true;
+    s->batch_last = BATCH_CG;
     if (!batch_engine_on(s)) return solve_cg_batch_seq(s, S, d_b, ldb, d_x, ldx, opt, res);
     for (int attempt = 0;; attempt++) {
         try {
@@ -322,7 +322,7 @@ int gg_transient_cg_batch(gg_solver *s, int nrhs, int nsteps, double h, const do
                           int *iters_total)
 {
     GG_API_BEGIN
-    return transient_batch(s, true, nrhs, nsteps, h, cdiag, src_off, src_node, src_kind, src_ptr, src_data, nport,
+    return transient_batch(s, BATCH_CG, nrhs, nsteps, h, cdiag, src_off, src_node, src_kind, src_ptr, src_data, nport,
                            port, x, opt, port_out, iters_total);
     GG_API_END
 }

@@ -1,5 +1,5 @@
 // gg_api.h -- the C ABI's exception boundary (solver.hip, dd.hip, batch.hip,
-// cg_batch.hip): an entry point's body between GG_API_BEGIN and GG_API_END
+// cg_batch.hip, bicgstab_batch.hip): an entry point's body between GG_API_BEGIN and GG_API_END
 // returns its own code, or the code of what it threw with the text left for
 // gg_last_error.
 #pragma once

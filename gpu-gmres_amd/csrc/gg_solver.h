@@ -1,9 +1,10 @@
 // gg_solver.h -- the single-device solver object behind the C ABI (solver.hip)
 // and what its engines in other files declare to each other: the many-RHS
-// batches (batch.hip: GMRES, cg_batch.hip: CG; the arena, read-back ring and
-// staging they share are batch_common.h's), the short-recurrence solves (cg.hip,
-// bicgstab.hip) and the read-back pipe, error-word triage and fallback they all
-// use.  The C ABI's exception boundary is gg_api.h.
+// batches (batch.hip: GMRES, cg_batch.hip: CG, bicgstab_batch.hip: BiCGStab; the
+// arena, read-back ring and staging they share are batch_common.h's), the
+// short-recurrence solves (cg.hip, bicgstab.hip) and the read-back pipe,
+// error-word triage and fallback they all use.  The C ABI's exception boundary
+// is gg_api.h.
 #pragma once
 
 #include <algorithm>
@@ -28,17 +29,28 @@ long long batch_history(gg_solver *s, int q, double *out, long long cap);
 // cg_batch.hip: the many-RHS conjugate-gradient engine behind
 // gg_solve_cg_batch_device (also the CG transient batch's step), its
 // per-scenario histories (batch_history hands over when the last batch ran
-// CG: s->batch_last_cg) and its work space
+// CG: s->batch_last) and its work space
 struct CgBatchWs;
 int solve_cg_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d_x, long long ldx,
                    const gg_options *opt, gg_result *res);
 long long cg_batch_history(gg_solver *s, int q, double *out, long long cap);
 void cg_batch_release(gg_solver *s);
-// batch.hip: the body of gg_transient_batch and gg_transient_cg_batch (cg: the
-// step solver is solve_cg_batch, its first chunk sized by the previous step)
-int transient_batch(gg_solver *s, bool cg, int nrhs, int nsteps, double h, const double *cdiag, const int *src_off,
-                    const int *src_node, const int *src_kind, const int *src_ptr, const double *src_data, int nport,
-                    const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total);
+// bicgstab_batch.hip: the same for BiCGStab, behind gg_solve_bicgstab_batch_device
+struct BiBatchWs;
+int solve_bicgstab_batch(gg_solver *s, int S, const double *d_b, long long ldb, double *d_x, long long ldx,
+                         const gg_options *opt, gg_result *res);
+long long bicgstab_batch_history(gg_solver *s, int q, double *out, long long cap);
+void bicgstab_batch_release(gg_solver *s);
+// the method of a batch: the last one's on the solver (s->batch_last;
+// gg_batch_history and gg_batch_mgs_kernel read it), a transient's step
+enum BatchMethod { BATCH_GMRES = 0, BATCH_CG = 1, BATCH_BICGSTAB = 2 };
+// batch.hip: the body of gg_transient_batch, gg_transient_cg_batch and
+// gg_transient_bicgstab_batch (method: the step's solver; CG's and BiCGStab's
+// first chunk is sized by the previous step)
+int transient_batch(gg_solver *s, BatchMethod method, int nrhs, int nsteps, double h, const double *cdiag,
+                    const int *src_off, const int *src_node, const int *src_kind, const int *src_ptr,
+                    const double *src_data, int nport, const int *port, double *x, const gg_options *opt,
+                    double *port_out, int *iters_total);
 // cg.hip, bicgstab.hip: the GG_SOLVE_CG and GG_SOLVE_BICGSTAB engines behind
 // solve_device (arguments checked by the caller, s->shared set); both are
 // short_recurrence.h's driver over their own launches
@@ -200,11 +212,13 @@ struct gg_solver {
     // the many-RHS solve's per-scenario arenas (batch.hip), kept between
     // batched solves of the same shape
     gg::BatchWs *batch = nullptr;
-    // the CG batch's (cg_batch.hip); batch_last_cg: gg_batch_history reads it;
-    // batch_iter_hint: the CG transient batch's previous step, the largest
-    // count of its scenarios (0: none)
+    // the CG batch's (cg_batch.hip) and the BiCGStab batch's (bicgstab_batch.hip);
+    // batch_last: the last batch's method, gg_batch_history reads it;
+    // batch_iter_hint: the CG or BiCGStab transient batch's previous step, the
+    // largest count of its scenarios (0: none)
     gg::CgBatchWs *cg_batch = nullptr;
-    bool batch_last_cg = false;
+    gg::BiBatchWs *bi_batch = nullptr;
+    gg::BatchMethod batch_last = gg::BATCH_GMRES;
     int batch_iter_hint = 0;
 };
 

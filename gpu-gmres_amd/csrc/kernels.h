@@ -50,9 +50,9 @@ struct UnitMap {
     long long tbase = 0, tn = 0;
 };
 
-// The many-RHS batch (batch.hip, cg_batch.hip) runs the launchers that take a
-// Batch on a grid (G, nsc), blockIdx.y = scenario: scenario q's per-scenario
-// buffers (vectors, partials, H, Givens, history, control block, hand-off
+// The many-RHS batch (batch.hip, cg_batch.hip, bicgstab_batch.hip) runs the
+// launchers that take a Batch on a grid (G, nsc), blockIdx.y = scenario:
+// scenario q's per-scenario buffers (vectors, partials, H, Givens, history, control block, hand-off
 // granules; the gate's done / nit likewise) lie q * zs bytes after scenario
 // 0's.  Same kernels and per-scenario arithmetic; the default is the single solve.
 // The batch's own kernels and loops (the launch_*_b at the end) take nsc and zs
@@ -397,17 +397,18 @@ constexpr int BI_WHY_RHO = 1, BI_WHY_RTV = 2, BI_WHY_OMEGA = 3;
 // launch_cg_pq (rt . v) and launch_cg_rz (t . s, then t . t).  it = the iteration's 0-based index.
 //   rtv = sum of part; zero or not finite: SR_BREAKDOWN; alpha = rho / rtv; r = s = (-alpha) v + r
 void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double *r, const double *v,
-                 long long Ppad, hipStream_t st);
+                 long long Ppad, hipStream_t st, Batch bt = {});
 //   ts, tt = sums of part_in; omega = tt > 0 ? ts / tt : 0; x = omega s + (alpha p + x);
 //   r = (-omega) t + s in place of s; part_out = block partials of r . r, then of rt . r
 void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, const double *p, double *s,
-                  const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st);
+                  const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st,
+                  Batch bt = {});
 //   rr, rhon = sums of part; resid = hist[it + 1] = sqrt(rr) / normb; resid < tol: SR_CONV; else omega or
 //   rhon zero or not finite: SR_BREAKDOWN; else p = ((rhon / rho) (alpha / omega)) ((-omega) v + p) + r.
 //   start (the initial residual, nothing counted; part = partials of r . r alone): hist[0], resid <= tol:
 //   SR_INIT, rho = rr zero or not finite: SR_BREAKDOWN, else rt = p = r
 void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
-                 const double *r, double *rt, double *hist, long long Ppad, hipStream_t st);
+                 const double *r, double *rt, double *hist, long long Ppad, hipStream_t st, Batch bt = {});
 
 // ---- batched (many-RHS) launches with kernels or loops of their own (the rest
 // of the batch runs the launchers above with a Batch): nsc scenarios per launch,
@@ -418,7 +419,8 @@ void launch_gather_b(const double *in, long long zin, const long long *idx, doub
                      long long n, int nsc, hipStream_t st);
 void launch_init_state_b(DevState *ds, long long zs, int nsc, double tol, int max_iter, int m, hipStream_t st);
 void launch_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol, int max_iter, hipStream_t st);
-// out[q] = scenario q's control block (DevState or CgState), q < nsc; the int at out + nsc = *err
+void launch_init_bi_state_b(BiState *bs, long long zs, int nsc, double tol, int max_iter, hipStream_t st);
+// out[q] = scenario q's control block (DevState, CgState or BiState), q < nsc; the int at out + nsc = *err
 template <class State>
 void launch_pack_states_b(const State *st0, long long zs, int nsc, State *out, const int *err, hipStream_t st);
 // u = each scenario's sources at time index it (soff: nsc + 1 offsets into the

@@ -1585,7 +1585,7 @@ __global__ void k_init_state_b(DevState *ds, long long zs, int nsc, double tol, 
     h.j = 1;
     *zp(ds, zs, q) = h;
 }
-// the scenarios' control blocks (DevState, CgState) side by side in a read-back
+// the scenarios' control blocks (DevState, CgState, BiState) side by side in a read-back
 // slot, and behind them the error word after every launch before this one
 // (batch_common.h ReadRing: one copy to the host per chunk)
 template <class State>
@@ -2945,6 +2945,7 @@ void launch_pack_states_b(const State *st0, long long zs, int nsc, State *out, c
 }
 template void launch_pack_states_b<DevState>(const DevState *, long long, int, DevState *, const int *, hipStream_t);
 template void launch_pack_states_b<CgState>(const CgState *, long long, int, CgState *, const int *, hipStream_t);
+template void launch_pack_states_b<BiState>(const BiState *, long long, int, BiState *, const int *, hipStream_t);
 void launch_transient_step_b(int n, int nsc, int maxsrc, const int *soff, const int *kind, const int *dptr,
                              const double *data, int it, double h, double *u, const int *sptr, const int *sidx,
                              const double *cdiag, const double *x, double *w, long long ldx, hipStream_t st)

@@ -20,8 +20,9 @@ namespace {
 // (every block forms the same scalars).  rz alternates between two words: the
 // launch that forms iteration it's beta from rz[it & 1] stores the next one.
 // (k_normb, k_cg_pq and k_cg_rz touch no control block: BiCGStab launches them too.)
-// zs: the many-RHS batch (cg_batch.hip), as k_dot -- grid (G, nsc), blockIdx.y
-// = scenario, every per-scenario pointer (vectors, partials, control block,
+// zs: the many-RHS batch (cg_batch.hip, bicgstab_batch.hip), as k_dot -- grid
+// (G, nsc), blockIdx.y = scenario, every per-scenario pointer (vectors,
+// partials, control block,
 // history, the gate's words) blockIdx.y * zs bytes on; the control block is
 // then written by thread 0 of block (0, scenario).  zs = 0: the single solve.
 __global__ void k_normb(const double *part, int G, double *normb, long long zs = 0)
@@ -226,15 +227,20 @@ __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, co
 // in flight, k_dot's order in every dot, no atomics, the control block written
 // by thread 0 of block 0 alone.  alpha and omega are stored by one launch and
 // read by later ones only; rho alternates between two words like CG's rz.
+// zs: the many-RHS batch (bicgstab_batch.hip), as the CG kernels above.
 __device__ __forceinline__ bool bi_bad(double v) { return !isfinite(v) || v == 0.0; }
 
 // rtv from the partials (breakdown when zero or not finite: nothing moves);
 // alpha = rho / rtv;  s = (-alpha) v + r in place of r
 __global__ __launch_bounds__(kBlock) void k_bi_s(Gate g, int it, BiState *bs, const double *part, int G,
                                                  double *__restrict__ r, const double *__restrict__ v,
-                                                 long long units)
+                                                 long long units, long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    bs = zp(bs, zs, blockIdx.y);
+    part = zp(part, zs, blockIdx.y);
+    r = zp(r, zs, blockIdx.y);
+    v = zp(v, zs, blockIdx.y);
     const long long stride = (long long)gridDim.x * kBlock;
     long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
     double2 rv[kUnroll], vv[kUnroll];
@@ -286,9 +292,17 @@ __global__ __launch_bounds__(kBlock) void k_bi_xr(Gate g, BiState *bs, const dou
                                                   double *__restrict__ x, const double *__restrict__ p,
                                                   double *__restrict__ s, const double *__restrict__ t,
                                                   const double *__restrict__ rt, double *part_out,
-                                                  long long units)
+                                                  long long units, long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    bs = zp(bs, zs, blockIdx.y);
+    part_in = zp(part_in, zs, blockIdx.y);
+    x = zp(x, zs, blockIdx.y);
+    p = zp(p, zs, blockIdx.y);
+    s = zp(s, zs, blockIdx.y);
+    t = zp(t, zs, blockIdx.y);
+    rt = zp(rt, zs, blockIdx.y);
+    part_out = zp(part_out, zs, blockIdx.y);
     const long long stride = (long long)gridDim.x * kBlock;
     long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
     double2 xv[kUnroll], pv[kUnroll], sv[kUnroll], tv[kUnroll], qv[kUnroll];
@@ -346,9 +360,16 @@ template <bool START>
 __global__ __launch_bounds__(kBlock) void k_bi_p(Gate g, int it, BiState *bs, const double *part, int G,
                                                  double *__restrict__ p, const double *__restrict__ v,
                                                  const double *__restrict__ r, double *__restrict__ rt,
-                                                 double *hist, long long units)
+                                                 double *hist, long long units, long long zs = 0)
 {
-    if (gated(g)) return;
+    if (gated_z(g, zs, blockIdx.y)) return;
+    bs = zp(bs, zs, blockIdx.y);
+    part = zp(part, zs, blockIdx.y);
+    p = zp(p, zs, blockIdx.y);
+    v = zp(v, zs, blockIdx.y);                      // (null at the start: never read there)
+    r = zp(r, zs, blockIdx.y);
+    rt = zp(rt, zs, blockIdx.y);                    // (null after the start: never written there)
+    hist = zp(hist, zs, blockIdx.y);
     const long long stride = (long long)gridDim.x * kBlock;
     long long u0 = blockIdx.x * (long long)kBlock + threadIdx.x;
     double2 pv[kUnroll], vv[kUnroll], rv[kUnroll];
@@ -422,6 +443,17 @@ __global__ void k_init_cg_state_b(CgState *cs, long long zs, int nsc, double tol
     *zp(cs, zs, q) = h;
 }
 
+// the BiCGStab batch's (bicgstab_batch.hip): every scenario's BiState
+__global__ void k_init_bi_state_b(BiState *bs, long long zs, int nsc, double tol, int max_iter)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nsc) return;
+    BiState h{};
+    h.tol = tol;
+    h.max_iter = max_iter;
+    *zp(bs, zs, q) = h;
+}
+
 }  // namespace
 
 // ======================================================= host launchers
@@ -456,22 +488,28 @@ void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, in
     else k_cg_p<false><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, bt.zs);
 }
 
-// ---- BiCGStab (bicgstab.hip) ------------------------------------------------------
-void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double *r, const double *v,
-                 long long Ppad, hipStream_t st)
+// ---- BiCGStab (bicgstab.hip, bicgstab_batch.hip) -----------------------------------
+void launch_init_bi_state_b(BiState *bs, long long zs, int nsc, double tol, int max_iter, hipStream_t st)
 {
-    k_bi_s<<<G, kBlock, 0, st>>>(g, it, bs, part, G, r, v, Ppad / 2);
+    k_init_bi_state_b<<<(nsc + 63) / 64, 64, 0, st>>>(bs, zs, nsc, tol, max_iter);
+}
+void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double *r, const double *v,
+                 long long Ppad, hipStream_t st, Batch bt)
+{
+    k_bi_s<<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, bs, part, G, r, v, Ppad / 2, bt.zs);
 }
 void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, const double *p, double *s,
-                  const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st)
+                  const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st, Batch bt)
 {
-    k_bi_xr<<<G, kBlock, 0, st>>>(g, bs, part_in, G, x, p, s, t, rt, part_out, Ppad / 2);
+    k_bi_xr<<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, bs, part_in, G, x, p, s, t, rt, part_out, Ppad / 2, bt.zs);
 }
 void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
-                 const double *r, double *rt, double *hist, long long Ppad, hipStream_t st)
+                 const double *r, double *rt, double *hist, long long Ppad, hipStream_t st, Batch bt)
 {
-    if (start) k_bi_p<true><<<G, kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2);
-    else k_bi_p<false><<<G, kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2);
+    if (start)
+        k_bi_p<true><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2, bt.zs);
+    else
+        k_bi_p<false><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2, bt.zs);
 }
 
 }  // namespace gg

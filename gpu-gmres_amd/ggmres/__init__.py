@@ -43,6 +43,7 @@ EXPORTS = [
     "gg_set_precond_ainv", "gg_set_precond_diag", "gg_ainv_fused", "gg_ainv_nnz", "gg_ainv_sliced",
     "gg_solve_cg_batch_device", "gg_solve_cg_batch", "gg_transient_cg_batch", "gg_batch_mgs_kernel",
     "gg_mgs_kernel_for",
+    "gg_solve_bicgstab_batch_device", "gg_solve_bicgstab_batch", "gg_transient_bicgstab_batch",
 ]
 # gg_precond_fn: int (*)(void *ctx, int op, const float *in, float *out, int n), device arrays
 PRECOND_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -164,6 +165,9 @@ def lib():
         L.gg_solve_cg_batch_device.argtypes = L.gg_solve_batch_device.argtypes
         L.gg_solve_cg_batch.argtypes = L.gg_solve_batch.argtypes
         L.gg_transient_cg_batch.argtypes = L.gg_transient_batch.argtypes
+        L.gg_solve_bicgstab_batch_device.argtypes = L.gg_solve_batch_device.argtypes
+        L.gg_solve_bicgstab_batch.argtypes = L.gg_solve_batch.argtypes
+        L.gg_transient_bicgstab_batch.argtypes = L.gg_transient_batch.argtypes
         L.gg_profile_enable.argtypes = [_VP, ctypes.c_int]
         L.gg_profile_reset.argtypes = [_VP]
         L.gg_profile_get.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
@@ -447,6 +451,23 @@ class Solver:
                                                    ctypes.byref(o), res), allow_nc=True)
         return self._batch_out(rc, res)
 
+    def solve_bicgstab_batch(self, B, X0=None, max_iter=3000, tol=1e-10, flags=SOLVE_BICGSTAB):
+        """solve_batch by BiCGStab (gg_solve_bicgstab_batch; A need not be
+        symmetric): the same dict, scenario q bit-identical to solve(B[q],
+        flags=SOLVE_BICGSTAB); ret EBREAKDOWN when a scenario broke down
+        (status per scenario)"""
+        return self._solve_batch(lib().gg_solve_bicgstab_batch, B, X0, 30, max_iter, tol, flags)
+
+    def solve_bicgstab_batch_device(self, b_ptr, x_ptr, nrhs, ld=None, max_iter=3000, tol=1e-10,
+                                    flags=SOLVE_BICGSTAB):
+        """solve_batch_device by BiCGStab (gg_solve_bicgstab_batch_device)"""
+        ld = self.n if ld is None else int(ld)
+        o = Options(30, int(max_iter), float(tol), int(flags))
+        res = (Result * int(nrhs))()
+        rc = _check(lib().gg_solve_bicgstab_batch_device(self.h, int(nrhs), _VP(b_ptr), ld, _VP(x_ptr), ld,
+                                                         ctypes.byref(o), res), allow_nc=True)
+        return self._batch_out(rc, res)
+
     def batch_history(self, q):
         """scenario q's residual history of the last batched solve (empty when
         the scenarios ran one by one: see history() after each)"""
@@ -470,6 +491,13 @@ class Solver:
         (gg_transient_cg_batch; A = G + C/h SPD): the same arguments and result"""
         return self._transient_batch(lib().gg_transient_cg_batch, nsteps, h, cdiag, scenarios, ports, X0, restart,
                                      max_iter, tol)
+
+    def transient_bicgstab_batch(self, nsteps, h, cdiag, scenarios, ports, X0, restart=32, max_iter=10000,
+                                 tol=1e-7):
+        """transient_batch with every step solved by BiCGStab
+        (gg_transient_bicgstab_batch): the same arguments and result"""
+        return self._transient_batch(lib().gg_transient_bicgstab_batch, nsteps, h, cdiag, scenarios, ports, X0,
+                                     restart, max_iter, tol)
 
     def _transient_batch(self, fn, nsteps, h, cdiag, scenarios, ports, X0, restart, max_iter, tol):
         S = len(scenarios)

@@ -160,7 +160,11 @@ typedef struct gg_options {
  * gg_solve_device_f32 and the gg_transient* loops, with GG_PRECOND_NONE, DIAG,
  * AINV, ILU0, ILUK or LU on any triangular-solve path and in any division
  * mode; GG_EINVAL together with GG_SOLVE_CG, with GG_PRECOND_SPLIT / USER /
- * USER_SPLIT, in gg_solve_batch* and in the sharded solve.  May be combined
+ * USER_SPLIT, in the sharded solve, and in gg_solve_batch* and
+ * gg_transient_batch, which define no flags: many right-hand sides are solved
+ * by BiCGStab through entry points of their own,
+ * gg_solve_bicgstab_batch_device, gg_solve_bicgstab_batch and
+ * gg_transient_bicgstab_batch (the many-RHS section below).  May be combined
  * with GG_SOLVE_SHARED_DEVICE under that flag's own conditions.
  * GG_EBREAKDOWN: rho or rt.v is zero or not finite (before anything moved in
  * that iteration), or omega or the next rho is while the solve has not
@@ -489,7 +493,8 @@ long long gg_batch_history(gg_solver *s, int rhs, double *out, long long cap);
  * launch; an odd last scenario on k_arnoldi_persist), k_arnoldi_persist<J, XG,
  * PF> (one launch per scenario), "" when the per-step kernels ran with every
  * scenario in each launch, when the scenarios ran one by one (gg_mgs_kernel
- * names theirs), after a CG batch or before the first batch; returns its length */
+ * names theirs), after a CG or BiCGStab batch or before the first batch;
+ * returns its length */
 int gg_batch_mgs_kernel(gg_solver *s, char *name, int cap);
 /* gg_transient_src for nrhs source scenarios at once, each its own source set,
  * all on the solver's A = G + C/h and cdiag: scenario q's sources are
@@ -533,6 +538,41 @@ int gg_transient_cg_batch(gg_solver *s, int nrhs, int nsteps, double h, const do
                           const int *src_node, const int *src_kind, const int *src_ptr, const double *src_data,
                           int nport, const int *port, double *x, const gg_options *opt, double *port_out,
                           int *iters_total);
+/* The many-RHS solve by BiCGStab (bicgstab_batch.hip): gg_solve_batch* with
+ * GG_SOLVE_BICGSTAB's method, for matrices that are not symmetric positive
+ * definite.  nrhs, ldb, ldx, the warm start in x and res[q] as above.
+ * opt->flags is GG_SOLVE_BICGSTAB or 0 -- both mean BiCGStab, the entry point
+ * names the method -- and any other bit GG_EINVAL (GG_SOLVE_CG included);
+ * opt->restart is validated in [1, 512] and otherwise ignored; opt->max_iter
+ * (>= 0) bounds each scenario's iterations.  GG_EINVAL for nrhs < 1 and a
+ * leading dimension below n, GG_ESTATE without a matrix or a preconditioner.
+ * Preconditioners as for GG_SOLVE_BICGSTAB (GG_EINVAL with GG_PRECOND_SPLIT /
+ * USER / USER_SPLIT).  Scenario q is exactly the single BiCGStab solve:
+ * status, iteration count, relres, history (gg_batch_history: the initial
+ * value, then one entry per iteration) and solution bits equal those of
+ * gg_solve_device(GG_SOLVE_BICGSTAB) on that right-hand side alone; res[q]:
+ * iters = inner_iters = its iterations, restarts = 0, status GG_OK,
+ * GG_NOT_CONVERGED or GG_EBREAKDOWN.  Batched when gg_batch_engine() = 1:
+ * per iteration two SpMVs, five BiCGStab launches and four wavefront
+ * triangular solves for all scenarios, a scenario that is over dropping out
+ * of them.  Otherwise the scenarios are solved one after the other by the
+ * single BiCGStab solve, with the same results.  A scenario that breaks down
+ * stops, the others run to their own end.  Returns GG_EBREAKDOWN if any
+ * scenario broke down (gg_last_error names the first one, its iteration, the
+ * scalar -- rho, rt.v or omega -- and its value), else 1 if any did not
+ * converge, else GG_OK; other values < 0 on error.  x holds every scenario's
+ * last iterate. */
+int gg_solve_bicgstab_batch_device(gg_solver *s, int nrhs, const double *d_b, long long ldb, double *d_x,
+                                   long long ldx, const gg_options *opt, gg_result *res);
+int gg_solve_bicgstab_batch(gg_solver *s, int nrhs, const double *b, long long ldb, double *x, long long ldx,
+                            const gg_options *opt, gg_result *res);   /* host arrays */
+/* gg_transient_batch with every step solved by gg_solve_bicgstab_batch_device
+ * (A = G + C/h need not be symmetric): the same arguments and results; a
+ * step's first chunk of iterations is sized by the previous step's counts. */
+int gg_transient_bicgstab_batch(gg_solver *s, int nrhs, int nsteps, double h, const double *cdiag,
+                                const int *src_off, const int *src_node, const int *src_kind, const int *src_ptr,
+                                const double *src_data, int nport, const int *port, double *x,
+                                const gg_options *opt, double *port_out, int *iters_total);
 
 /* Diagnostics: run one wavefront triangular solve (which: 0 = L / Ml, 1 = U / Mr)
  * on the current right-hand side and return, per band, the device real-time
