@@ -161,6 +161,7 @@ constexpr int kWaveTAlign = 32;
 // 3D tiles: steps per tile padded to whole pairs of 8-step batches (k_trsv_tile3d)
 constexpr int kTileTAlign = 16;
 constexpr int kTileDummyBlocks = 2048;   // workgroups with their own dummy granules (grid cap)
+constexpr int kWaveXcdWord = 16;         // words per 2D band's XCD word (a 128-B line of its own)
 struct Wave2D {
     bool ok = false;
     int nx = 0, ny = 0, nz = 1, nbands = 0, T = 0;
@@ -378,6 +379,11 @@ struct DevTri {
         return (fast && mul_ok && div != WD_UNIT) ? (int)WD_MUL : div;
     }
     DBuf<unsigned long long> bnd;  // nbands * T hand-off granules (sentinel = not ready) + 128 dummies
+    // 2D bands: per band one 128-B line behind bnd's task queue words, whose first
+    // word is (launch number << 4 | 8 | XCD) of the band's workgroup (kernels/
+    // trsv_wave.hip, the hand-off through the XCD's own L2); xseq = launches so far
+    unsigned long long *xw = nullptr;
+    unsigned long long xseq = 0;
     DBuf<unsigned long long> fcnt; // fused SpMV (forward solve): per slice group, 1 = stored (0 between launches)
     long long *trace = nullptr;  // diagnostics: per band, nbatch+1 timestamps (gg_trace_precond)
     double bytes = 0;            // algorithmic bytes per solve

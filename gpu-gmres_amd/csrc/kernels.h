@@ -254,6 +254,11 @@ bool launch_spmv_xdiv(Gate g, const DevCsr &A, const double *x, const double *xd
 
 // ---- triangular solves ---------------------------------------------------------
 void launch_trsv(Gate g, DevTri &T, const double *b, double *x, int *err, hipStream_t st);
+// the candidate workgroup (of wave_band_candidates() per band) that runs band number k of
+// nbands in dependency order when the bands are dealt in ng contiguous groups
+// (kernels/trsv_wave.hip, GG_WAVE_NG_U / _L); -1 for arguments out of range
+int wave_band_candidate(int nbands, int ng, int k);
+int wave_band_candidates();
 // forward solve of w = A v on the 2D wavefront, the SpMV fused into the launch
 // (GG_FUSE_SPMV): fused_spmv_ok says whether triangle T and A admit it
 bool fused_spmv_ok(const DevTri &T, const DevCsr &A);

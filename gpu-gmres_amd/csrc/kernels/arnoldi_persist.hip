@@ -221,17 +221,7 @@ __device__ __forceinline__ bool gather_h_first(const unsigned long long *row, un
 // runs on (HW_REG_XCC_ID), which only a reducer ON that XCD writes.  8 pollers
 // of the G-granule row instead of G.
 constexpr int kXcdSlot = 16;                 // words per XCD slot (own 128-B line)
-constexpr int kXcds = 8;
-__device__ __forceinline__ unsigned xcc_id()
-{
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return v & (kXcds - 1);
-}
-__device__ __forceinline__ void st_plain(unsigned long long *p, unsigned long long v)
-{
-    asm volatile("global_store_dwordx2 %0, %1, off" ::"v"(p), "v"(v) : "memory");
-}
+// (kXcds, xcc_id(), st_plain(): device.h)
 // this block's role for the launch: the first block of its XCD to raise the
 // XCD's election word to `seq` (strictly increasing per launch) reduces
 __device__ __forceinline__ void xcd_elect(unsigned long long *elect, unsigned long long seq, bool &red,

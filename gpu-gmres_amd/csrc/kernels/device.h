@@ -251,6 +251,24 @@ __device__ __forceinline__ void st_agent_d(double *p, double v)
     st_agent(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v));
 }
 
+// ---- hand-offs inside one XCD ---------------------------------------------------
+// A plain store (no sc bits) stops in the L2 of the XCD that issued it, where an
+// agent-scope (sc1) poll from the same XCD finds it: 234 ns one way against 470
+// for an sc1 store (profiles/r04/r04_xcd_handoff.txt).  Only for a reader known
+// to run on the writer's XCD (HW_REG_XCC_ID of both): another XCD sees the
+// value only once the line is written back.
+constexpr int kXcds = 8;
+__device__ __forceinline__ unsigned xcc_id()
+{
+    unsigned v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+    return v & (kXcds - 1);
+}
+__device__ __forceinline__ void st_plain(unsigned long long *p, unsigned long long v)
+{
+    asm volatile("global_store_dwordx2 %0, %1, off" ::"v"(p), "v"(v) : "memory");
+}
+
 // 16 bytes stored write-through (two agent-scope 8-byte stores, sc1): visible
 // to other XCDs once drained.  (Not inline asm: the compiler does not guard an
 // asm store's data registers against the VALU write hazard that follows it.)

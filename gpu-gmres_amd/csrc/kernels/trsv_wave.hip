@@ -124,6 +124,46 @@ constexpr int kWaveLoaders = GG_WAVE_LOADERS;
 #ifndef GG_WAVE_XCD
 #define GG_WAVE_XCD 4
 #endif
+// Hand-off through the XCD's own L2 (2D single solves).  GG_WAVE_NG_U
+// / GG_WAVE_NG_L = NG > 0 for the backward / forward solve: kWaveCand candidate
+// workgroups are dealt per band and band number k of the dependency order runs
+// in candidate k * NG / nbands (wave_candidate), so -- workgroups being dealt
+// round-robin over the XCDs -- NG contiguous groups of bands share an XCD each;
+// every band publishes its XCD (xcc_id) in a word tagged with the launch's
+// number, and a writer wave whose consumer band's word names its own XCD
+// publishes the edge granules with a plain store (st_plain, device.h) instead
+// of the sc1 one.  The protocol never relies on the placement: a consumer
+// whose word is not known yet, or names another XCD, gets sc1 stores.
+// 0: the placement above (GG_WAVE_XCD; forward: one workgroup per band) and
+// sc1 stores only.
+#ifndef GG_WAVE_NG_U
+#define GG_WAVE_NG_U 0
+#endif
+#ifndef GG_WAVE_NG_L
+#define GG_WAVE_NG_L 2
+#endif
+constexpr int kWaveCand = 8;                // candidate workgroups per band: one per XCD
+static_assert(GG_WAVE_NG_U >= 0 && GG_WAVE_NG_U <= kWaveCand && GG_WAVE_NG_L >= 0 && GG_WAVE_NG_L <= kWaveCand,
+              "groups of bands: at most one per candidate");
+// the candidate that runs band number k (of nbands, in dependency order) with ng groups
+__host__ __device__ constexpr int wave_candidate(int nbands, int ng, int k)
+{
+    return (int)((long long)k * ng / nbands);
+}
+// groups of a direction's 2D single solve (0: no dealing by groups) and the
+// workgroups its launch holds per band -- the kernel and its launchers both
+// take them from here
+constexpr int wave_groups(bool fwd) { return fwd ? GG_WAVE_NG_L : GG_WAVE_NG_U; }
+constexpr int wave_deal(bool fwd) { return wave_groups(fwd) > 0 ? kWaveCand : fwd ? 1 : GG_WAVE_XCD; }
+// The fused SpMV + L launch deals by groups for the unit L's fused rows (ILU(0)
+// grids) only: the split engine's launch divides in its SpMV blocks' gathers,
+// and with the CUs that the candidates take from them its bands wait for b
+// (bench.py --workload pg, one run each: 4,169 -> 4,100 it/s with the dealing).
+constexpr int wave_deal_fs(int div) { return div == WD_UFMA ? wave_deal(true) : 1; }
+// CUs per band that the launch's SpMV blocks leave free
+#ifndef GG_WAVE_FS_SPARE
+#define GG_WAVE_FS_SPARE (wave_deal_fs(WD_UFMA))
+#endif
 // Redundant compute waves: GG_WAVE_NC waves (on distinct SIMDs) run the same
 // recurrence on the same operands -- bit-identical values -- and wave c stages
 // only the step pairs kk with kk % NC == c for the writer wave.  A single
@@ -393,7 +433,7 @@ __device__ __forceinline__ void trsv_wave2d_body(
     double *__restrict__ x, unsigned long long *bnd, int *err, long long *trace,
     int nz, long long P2, const double *__restrict__ c0, unsigned long long *prog,
     const double *__restrict__ ce1, const double *__restrict__ ce2, const FusedSpmv &fs,
-    int zS = 1, long long zs = 0, int zmap = 0)
+    int zS = 1, long long zs = 0, int zmap = 0, unsigned long long *xw = nullptr, unsigned long long xseq = 0)
 {
     using C = WaveCfg<DIV, D3, S>;
     // LDS work in the lane shift's shadow -- not for the unit L's fused rows,
@@ -451,10 +491,17 @@ __device__ __forceinline__ void trsv_wave2d_body(
     // Measured on C2: U 121.0 -> 117.9 us, while L (3 streamed arrays) slows
     // 88.9 -> 90.0 us (round 3, re-measured: 89.4 / 90.3 -> 89.9 / 90.4 us), so
     // the forward solve keeps one workgroup per band.
-    // (the fused SpMV's launch holds one workgroup per band: no placement there)
-    constexpr int XS = (D3 || FS || FWD || BT) ? 1 : GG_WAVE_XCD;
-    if (XS > 1 && bid % XS) return;
+    // GG_WAVE_NG_U / _L = NG > 0: kWaveCand workgroups per band, the one of the
+    // band's group running it (the fused SpMV's launch too: its other
+    // candidates exit, the SpMV blocks keep the low indices).
+    constexpr bool GRP = !D3 && !BT && !(FS && wave_deal_fs(DIV) == 1);
+    constexpr int NG = GRP ? wave_groups(FWD) : 0;
+    constexpr int XS = (D3 || BT) ? 1 : FS ? wave_deal_fs(DIV) : wave_deal(FWD);
+    if (XS > 1 && bid % XS != (NG > 0 ? wave_candidate(nbands, NG, bid / XS) : 0)) return;
     const int blk = bid / XS;
+    // the hand-off through the XCD's L2: compiled for NG > 0, run where the
+    // launcher passes the bands' XCD words
+    constexpr bool L2H = NG > 0;
     const int ntask = nz * nbands;
     for (int task = blk; task < ntask; task += ((FS || BT) ? nbands : (int)gridDim.x / XS)) {
     const int kq = task / nbands, bq = task % nbands;
@@ -553,10 +600,45 @@ __device__ __forceinline__ void trsv_wave2d_body(
         // upstream must not hold back what it hands downstream.
         double2 *X2 = reinterpret_cast<double2 *>(x) + boff;
         [[maybe_unused]] bool bad = false;  // WD_RCP range guard (see rcp_safe)
+        // L2H: this band's XCD goes into its word (sc1, tagged with the launch's
+        // number: a word left by an earlier or a gated launch reads as unknown);
+        // the consumer band's word is requested here and looked at when the first
+        // batch is published, then once per batch until it carries this launch's
+        // tag -- no spin, and an unknown consumer simply gets sc1 stores.  local:
+        // the consumer runs on this XCD, so its sc1 polls are served by the L2
+        // that a plain store stops in.
+        [[maybe_unused]] unsigned long long cword = 0;
+        [[maybe_unused]] const unsigned long long *cwp = nullptr;
+        [[maybe_unused]] unsigned myx = 0;
+        [[maybe_unused]] bool cknown = false, local = false;
+        [[maybe_unused]] long long nlocal = 0;
+        if constexpr (L2H || TRACE) myx = xcc_id();
+        if constexpr (L2H) {
+            if (xw) {
+                if (lane == 0) st_agent(xw + (long long)band * kWaveXcdWord, (xseq << 4) | 8ull | myx);
+                if (is_prod) {
+                    cwp = xw + (long long)(FWD ? band + 1 : band - 1) * kWaveXcdWord;
+                    cword = ld_agent(cwp);
+                }
+            }
+        }
         for (int bi = 0; bi <= nbatch; bi++) {
             if (!GG_WAVE_DECOUPLE || bi == 0) raw_barrier();
             if (bi == 0) continue;
             const int pb = bi - 1;
+            if constexpr (L2H) {
+                if (cwp && !cknown) {
+                    const unsigned long long cw =
+                        (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cword) |
+                        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(cword >> 32)) << 32);
+                    if ((cw >> 4) == xseq && (cw & 8ull)) {
+                        cknown = true;
+                        local = (unsigned)(cw & 7ull) == myx;
+                    } else {
+                        cword = ld_agent(cwp);      // looked at with the next batch
+                    }
+                }
+            }
             if constexpr (GG_WAVE_DECOUPLE) {
                 while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&xdone, __ATOMIC_RELAXED,
                                                                         __HIP_MEMORY_SCOPE_WORKGROUP)) <= seq + pb)
@@ -573,8 +655,10 @@ __device__ __forceinline__ void trsv_wave2d_body(
                 [FWD ? (tt & 1) : 1 - (tt & 1)];
             if (is_prod && lane < C::B) {
                 const int t = FWD ? pb * C::B + tt : (T - 1) - (pb * C::B + tt);
-                st_agent(pub + t, (unsigned long long)__double_as_longlong(e));
+                if (L2H && local) st_plain(pub + t, (unsigned long long)__double_as_longlong(e));
+                else st_agent(pub + t, (unsigned long long)__double_as_longlong(e));
             }
+            if constexpr (TRACE) nlocal += (L2H && local && is_prod) ? 1 : 0;
             double2 v[C::PBN];
 #pragma unroll
             for (int kk = 0; kk < C::PBN; kk++) v[kk] = xb[kk * 64 + lane];
@@ -596,6 +680,13 @@ __device__ __forceinline__ void trsv_wave2d_body(
             if constexpr (GG_WAVE_DECOUPLE) raw_barrier();     // barrier bi (the last: the final one)
         }
         seq += nbatch;
+        if constexpr (TRACE) {
+            // the band's XCD + 1, the groups compiled in, the batches published
+            // with plain stores (ggmres.h, gg_trace_precond)
+            if (lane == 0)
+                trace[(long long)band * (3 * nbatch + 8) + nbatch + 7] =
+                    (long long)(myx + 1) | ((long long)NG << 4) | (nlocal << 8);
+        }
         if constexpr (D3) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) st_agent(prog_mine, (unsigned long long)nbatch);
@@ -912,10 +1003,11 @@ __global__ __launch_bounds__((WaveCfg<DIV, D3, S>::THREADS)) void k_trsv_wave2d(
     const double *__restrict__ c2, const double *__restrict__ dv, const double *__restrict__ rv,
     double *__restrict__ x, unsigned long long *bnd, int *err, long long *trace,
     int nz, long long P2, const double *__restrict__ c0, unsigned long long *prog,
-    const double *__restrict__ ce1, const double *__restrict__ ce2)
+    const double *__restrict__ ce1, const double *__restrict__ ce2, unsigned long long *xw,
+    unsigned long long xseq)
 {
     trsv_wave2d_body<FWD, DIV, TRACE, D3, S, IL, false>(g, T, nbands, b, c1, c2, dv, rv, x, bnd, err, trace, nz,
-                                                        P2, c0, prog, ce1, ce2, FusedSpmv{});
+                                                        P2, c0, prog, ce1, ce2, FusedSpmv{}, 1, 0, 0, xw, xseq);
 }
 
 // forward 2D solve with b = A v computed by the launch's blocks < fs.ns (FusedSpmv)
@@ -923,11 +1015,12 @@ template <int DIV>
 __global__ __launch_bounds__((WaveCfg<DIV>::THREADS)) void k_trsv_wave2d_spmv(
     Gate g, int T, int nbands, const double *__restrict__ c1, const double *__restrict__ c2,
     const double *__restrict__ dv, const double *__restrict__ rv, double *__restrict__ x,
-    unsigned long long *bnd, int *err, long long P2, FusedSpmv fs)
+    unsigned long long *bnd, int *err, long long P2, FusedSpmv fs, unsigned long long *xw,
+    unsigned long long xseq)
 {
     trsv_wave2d_body<true, DIV, false, false, 1, false, true>(g, T, nbands, fs.w, c1, c2, dv, rv, x, bnd, err,
                                                               nullptr, 1, P2, nullptr, nullptr, nullptr, nullptr,
-                                                              fs);
+                                                              fs, 1, 0, 0, xw, xseq);
 }
 
 // batched 2D solve (the many-RHS solve): zS scenarios, nbands workgroups each
@@ -1510,6 +1603,13 @@ static int tile_grid_override(int g)
     return e && atoi(e) > 0 ? atoi(e) : g;
 }
 
+int wave_band_candidate(int nbands, int ng, int k)
+{
+    if (nbands < 1 || ng < 1 || ng > kWaveCand || k < 0 || k >= nbands) return -1;
+    return wave_candidate(nbands, ng, k);
+}
+int wave_band_candidates() { return kWaveCand; }
+
 int wave_batch_steps(int div, bool d3, int skew)
 {
     // WD_MUL streams as many arrays as WD_HW (y in d's place): the same batches
@@ -1546,7 +1646,13 @@ void launch_trsv_spmv(Gate g, DevTri &T, const DevCsr &A, const double *v, doubl
     }
     // every CU the bands leave free computes b (the SpMV blocks wait on nothing)
     static const int cus = device_cus();
-    const int ns = std::max(64, cus - wl.nbands);
+    // (of a band's wave_deal candidate workgroups all but one exit at once, but
+    // the dispatcher deals them all: GG_WAVE_FS_SPARE CUs per band stay free of
+    // SpMV blocks, so that the XCD of a group has room for its bands)
+    const int deal = wave_deal_fs(T.eff_div());
+    const int ns = std::max(64, cus - wl.nbands * (deal > 1 ? GG_WAVE_FS_SPARE : 1));
+    const int nwg = wl.nbands * deal + ns;
+    const unsigned long long xseq = ++T.xseq;
     FusedSpmv fs;
     fs.sptr = A.sptr.p;
     fs.sci = A.sci.p;
@@ -1559,11 +1665,11 @@ void launch_trsv_spmv(Gate g, DevTri &T, const DevCsr &A, const double *v, doubl
     fs.n = A.n;
     fs.ns = ns;
     if (T.eff_div() == WD_UFMA)
-        k_trsv_wave2d_spmv<WD_UFMA><<<wl.nbands + ns, WaveCfg<WD_UFMA>::THREADS, 0, st>>>(
-            g, wl.T, wl.nbands, T.c1.p, T.c2.p, nullptr, nullptr, x, T.bnd.p, err, wl.P2, fs);
+        k_trsv_wave2d_spmv<WD_UFMA><<<nwg, WaveCfg<WD_UFMA>::THREADS, 0, st>>>(
+            g, wl.T, wl.nbands, T.c1.p, T.c2.p, nullptr, nullptr, x, T.bnd.p, err, wl.P2, fs, T.xw, xseq);
     else   // the split engine's non-unit L, coefficients and b pre-scaled by RN(1/d)
-        k_trsv_wave2d_spmv<WD_SFMA><<<wl.nbands + ns, WaveCfg<WD_SFMA>::THREADS, 0, st>>>(
-            g, wl.T, wl.nbands, T.c1s.p, T.c2s.p, T.rw.p, nullptr, x, T.bnd.p, err, wl.P2, fs);
+        k_trsv_wave2d_spmv<WD_SFMA><<<nwg, WaveCfg<WD_SFMA>::THREADS, 0, st>>>(
+            g, wl.T, wl.nbands, T.c1s.p, T.c2s.p, T.rw.p, nullptr, x, T.bnd.p, err, wl.P2, fs, T.xw, xseq);
 }
 
 void launch_trsv_one(Gate g, DevTri &T, const double *b, double *x, int *err, hipStream_t st)
@@ -1577,16 +1683,17 @@ void launch_trsv_one(Gate g, DevTri &T, const double *b, double *x, int *err, hi
         const double *dv = (div == WD_UNIT || div == WD_UFMA) ? nullptr
                          : (div == WD_MUL || div == WD_SFMA) ? T.rw.p : T.dw.p;
         const double *rv = div == WD_RCP ? T.rw.p : nullptr;
+        const unsigned long long xseq = ++T.xseq;       // the launch's number (the bands' XCD words)
         if ((div == WD_UFMA || div == WD_SFMA) && !w.tile) {
             // GG_DIV_FMA on a 2D grid (build_tri admits unskewed ones in canonical order)
-            dim3 grid(w.nbands * (T.lower ? 1 : GG_WAVE_XCD));
+            dim3 grid(w.nbands * wave_deal(T.lower));
             const double *k1 = div == WD_SFMA ? T.c1s.p : T.c1.p, *k2 = div == WD_SFMA ? T.c2s.p : T.c2.p;
             if (w.skew > 1) {
                 // ILU(k) grids (skewed lanes): the fills pre-scaled with U's coefficients
                 const double *f1 = div == WD_SFMA ? T.ce1s.p : T.ce1.p, *f2 = div == WD_SFMA ? T.ce2s.p : T.ce2.p;
 #define GG_FMA_SKEW_LAUNCH(FWD, DIV, S)                                                            \
     k_trsv_wave2d<FWD, DIV, false, false, S, false><<<grid, WaveCfg<DIV, false, S>::THREADS, 0, st>>>( \
-        g, w.T, w.nbands, b, k1, k2, dv, rv, x, T.bnd.p, err, nullptr, 1, w.P2, nullptr, nullptr, f1, f2)
+        g, w.T, w.nbands, b, k1, k2, dv, rv, x, T.bnd.p, err, nullptr, 1, w.P2, nullptr, nullptr, f1, f2, T.xw, xseq)
                 if (T.lower && div == WD_UFMA) {
                     if (w.skew == 2) GG_FMA_SKEW_LAUNCH(true, WD_UFMA, 2);
                     else GG_FMA_SKEW_LAUNCH(true, WD_UFMA, 3);
@@ -1605,7 +1712,7 @@ void launch_trsv_one(Gate g, DevTri &T, const double *b, double *x, int *err, hi
 #define GG_FMA_LAUNCH(FWD, DIV, TR)                                                                \
     k_trsv_wave2d<FWD, DIV, TR><<<grid, WaveCfg<DIV>::THREADS, 0, st>>>(                           \
         g, w.T, w.nbands, b, k1, k2, dv, rv, x, T.bnd.p, err, T.trace, 1, w.P2, nullptr, nullptr,   \
-        nullptr, nullptr)
+        nullptr, nullptr, T.xw, xseq)
             // (T.il needs no instantiation of its own: the fused rows take the
             // in-line term first in either canonical order)
             if (T.lower && div == WD_UFMA) {
@@ -1655,17 +1762,17 @@ void launch_trsv_one(Gate g, DevTri &T, const double *b, double *x, int *err, hi
             }
 #undef GG_TILE_LAUNCH
         } else if (w.nz == 1) {
-            dim3 grid(w.nbands * (T.lower ? 1 : GG_WAVE_XCD));
+            dim3 grid(w.nbands * wave_deal(T.lower));
 #define GG_WAVE_LAUNCH_S(FWD, DIV, S, IL)                                                          \
     k_trsv_wave2d<FWD, DIV, false, false, S, IL><<<grid, WaveCfg<DIV, false, S>::THREADS, 0, st>>>( \
         g, w.T, w.nbands, b, T.c1.p, T.c2.p, dv, rv, x, T.bnd.p, err, nullptr, 1, w.P2, nullptr,   \
-        nullptr, T.ce1.p, T.ce2.p)
+        nullptr, T.ce1.p, T.ce2.p, T.xw, xseq)
 #define GG_WAVE_LAUNCH(FWD, DIV)                                                                   \
     do {                                                                                           \
         if (T.trace && w.skew == 1 && !T.il)                                                       \
             k_trsv_wave2d<FWD, DIV, true><<<grid, WaveCfg<DIV>::THREADS, 0, st>>>(                 \
                 g, w.T, w.nbands, b, T.c1.p, T.c2.p, dv, rv, x, T.bnd.p, err, T.trace, 1, w.P2,     \
-                nullptr, nullptr, nullptr, nullptr);                                               \
+                nullptr, nullptr, nullptr, nullptr, T.xw, xseq);                                               \
         else if (T.il)                                                                             \
             GG_WAVE_LAUNCH_S(FWD, DIV, 1, true);                                                   \
         else if (w.skew == 1)                                                                      \
@@ -1696,7 +1803,7 @@ void launch_trsv_one(Gate g, DevTri &T, const double *b, double *x, int *err, hi
         const int grid = std::min(std::min(ntask, wave3d_max_blocks<FWD, DIV>()), kTileDummyBlocks); \
         k_trsv_wave2d<FWD, DIV, false, true><<<grid, WaveCfg<DIV, true>::THREADS, 0, st>>>(        \
             g, w.T, w.nbands, b, T.c1.p, T.c2.p, dv, rv, x, T.bnd.p, err, nullptr, w.nz, w.P2,      \
-            T.c0.p, T.prog.p, nullptr, nullptr);                                                   \
+            T.c0.p, T.prog.p, nullptr, nullptr, nullptr, 0ull);                                                   \
     } while (0)
             if (T.lower) {
                 if (div == WD_UNIT) GG_WAVE_LAUNCH3(true, WD_UNIT);

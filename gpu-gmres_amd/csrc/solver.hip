@@ -430,12 +430,16 @@ void build_tri(DevTri &T, const CanonTri &C, const Wave2D *wl, const std::vector
         // zero granules (dummy reads) and 64 write-only ones (dummy re-arms),
         // for up to kTileDummyBlocks workgroups: one line that every boundary
         // wave polled and re-armed would be a hot spot on one memory channel
-        // (+ 64 words: the 3D tile kernel's task queue, k_trsv_tile3d)
+        // (+ 64 words: the 3D tile kernel's task queue, k_trsv_tile3d; + one
+        // 128-B line per 2D band: the word that names its workgroup's XCD)
         const long long ngran = wl->ngran();
         const long long ndummy = 128LL * kTileDummyBlocks;
-        T.bnd.alloc((size_t)(ngran + ndummy + 64));
+        const long long nxw = (wl->tile || wl->nz != 1) ? 0 : kWaveXcdWord * (long long)wl->nbands;
+        T.bnd.alloc((size_t)(ngran + ndummy + 64 + nxw));
         launch_fill_u64(T.bnd.p, ngran, kSentinel, st);
-        launch_fill_u64(T.bnd.p + ngran, ndummy + 64, 0ull, st);
+        launch_fill_u64(T.bnd.p + ngran, ndummy + 64 + nxw, 0ull, st);
+        T.xw = nxw ? T.bnd.p + ngran + ndummy + 64 : nullptr;
+        T.xseq = 0;
         // algorithmic bytes: this triangle's share of B_ilu --
         // its CSR entries (a stored diagonal included), one row-pointer array, b
         // read and x written -- the reference's formulation of the same solve
@@ -2835,6 +2839,11 @@ int gg_trace_precond(gg_solver *s, int which, long long *out, long long cap, int
     *nbatch = nbt;
     return GG_OK;
     GG_API_END
+}
+
+int gg_wave_band_candidate(int nbands, int ngroups, int k)
+{
+    return gg::wave_band_candidate(nbands, ngroups, k);
 }
 
 int gg_profile_enable(gg_solver *s, int kinds)

@@ -33,7 +33,7 @@ EXPORTS = [
     "gg_uses_wavefront", "gg_solve", "gg_solve_device", "gg_get_history", "gg_spmv",
     "gg_precond_apply", "gg_time_spmv", "gg_time_precond", "gg_bytes_spmv",
     "gg_bytes_precond", "gg_profile_enable", "gg_profile_reset", "gg_profile_get",
-    "gg_trace_precond", "gg_bytes_trsv", "gg_bytes_trsv_stream", "gg_transient", "gg_set_precond_ilu0_device",
+    "gg_trace_precond", "gg_wave_band_candidate", "gg_bytes_trsv", "gg_bytes_trsv_stream", "gg_transient", "gg_set_precond_ilu0_device",
     "gg_ilu0_device_values", "gg_set_precond_iluk_device", "gg_iluk_device_factors",
     "gg_transient_src", "gg_transient_set_taps", "gg_transient_get_taps", "gg_spmv_sliced", "gg_spmv_panels", "gg_spmv_rtile",
     "gg_transient_mna", "gg_set_division", "gg_division_active",
@@ -141,6 +141,7 @@ def lib():
         L.gg_trace_precond.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong),
                                        ctypes.c_longlong, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)]
+        L.gg_wave_band_candidate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.gg_bytes_spmv.argtypes = [_VP]
         L.gg_bytes_spmv.restype = ctypes.c_double
         L.gg_bytes_precond.argtypes = [_VP]

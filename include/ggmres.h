@@ -580,11 +580,21 @@ int gg_transient_bicgstab_batch(gg_solver *s, int nrhs, int nsteps, double h, co
  * core-cycle totals of four phases of the compute wave's batches (barrier wait,
  * batch top to first result, first to last result, last result to the next
  * barrier), the boundary wave's poll retries and the core cycles it spent
- * retrying, one spare slot, then the real-time stamps at which the writer wave
- * published each batch and at which the boundary wave saw each batch's
- * values: out[band * (3 * nbatch + 8) + k].  GG_ESTATE unless the wavefront path is active. */
+ * retrying, one word on the band's placement and outgoing hand-off (2D bands;
+ * k = nbatch + 7: bits 0-3 the XCD the band ran on + 1, bits 4-7 the number of
+ * contiguous band groups the direction is built with, 0 = none, bits 8 and up
+ * the batches whose edge values it published with plain stores through its
+ * XCD's L2 -- 0: every batch with write-through stores), then the real-time
+ * stamps at which the writer wave published each batch and at which the
+ * boundary wave saw each batch's values: out[band * (3 * nbatch + 8) + k].
+ * GG_ESTATE unless the wavefront path is active. */
 int gg_trace_precond(gg_solver *s, int which, long long *out, long long cap, int *nbands,
                      int *nbatch);
+/* The 2D wavefront solves deal 8 candidate workgroups per band, one per XCD;
+ * with the bands in ngroups contiguous groups (1..8), band number k of nbands
+ * (in dependency order) runs in the candidate this returns, so the bands of a
+ * group share an XCD.  -1 for arguments out of range.  Host-side, no device. */
+int gg_wave_band_candidate(int nbands, int ngroups, int k);
 
 #ifdef __cplusplus
 }

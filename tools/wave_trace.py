@@ -36,6 +36,9 @@ for which in (0, 1):
     comp = (raw[:, :nbt + 1] - t0) * 0.01           # us
     ph = raw[:, nbt + 1:nbt + 5].astype(np.float64)
     bw = raw[:, nbt + 5:nbt + 7].astype(np.float64)
+    # placement word (ggmres.h): XCD + 1, band groups built in, batches published with plain stores
+    pw = raw[:, nbt + 7]
+    xcd, ngrp, nloc = (pw & 15) - 1, int((pw[0] >> 4) & 15), pw >> 8
     pub = (raw[:, nbt + 8:2 * nbt + 8] - t0) * 0.01
     seen = (raw[:, 2 * nbt + 8:3 * nbt + 8] - t0) * 0.01
     start, end = comp[:, 0], comp[:, -1]
@@ -47,7 +50,7 @@ for which in (0, 1):
           np.round(ph.mean(axis=0) / nbt, 0).tolist())
     print("  boundary retries/batch per band:", np.round(bw[:, 0] / nbt, 2).tolist())
     # hand-off: consumer batch bi needs producer steps up to KB*bi+KB-1+63 -> producer batch
-    lat, ahead = [], []
+    lat, ahead, loc = [], [], []
     for c in range(nb):
         p = c - 1 if which == 0 else c + 1
         if p < 0 or p >= nb:
@@ -57,9 +60,16 @@ for which in (0, 1):
             if k < nbt:
                 lat.append(seen[c, bi] - pub[p, k])
                 ahead.append(comp[c, bi] - seen[c, bi])
-    lat = np.array(lat)
+                loc.append(nloc[p] > 0)
+    lat, loc = np.array(lat), np.array(loc)
+    print(f"  placement: band groups {ngrp}, XCD per band {xcd.tolist()}")
+    print(f"  hand-off mode per producer band (batches through the XCD's L2 of {nbt}): {nloc.tolist()}")
     print(f"  publish -> seen latency us: median {np.median(lat):.2f} p10 {np.percentile(lat, 10):.2f} "
           f"p90 {np.percentile(lat, 90):.2f}")
+    for name, m in (("local (plain store)", loc), ("sc1 store", ~loc)):
+        if m.any():
+            print(f"    {name}: {int(m.sum())} batches, median {np.median(lat[m]):.2f} "
+                  f"p10 {np.percentile(lat[m], 10):.2f} p90 {np.percentile(lat[m], 90):.2f}")
     print(f"  seen -> consumer batch start us: median {np.median(ahead):.2f}")
     wr = []
     for c in range(nb):
