@@ -17,6 +17,12 @@
 // is enqueued on the main stream between the (gated) kernels, so a whole
 // restart cycle is enqueued with one host read of the control block per
 // cycle, as solver.hip.
+//
+// GG_SOLVE_CG ("short-recurrence methods on shards" below; DESIGN.md "Sharded
+// CG"): the same SpMV, apply and exchanges around cg.hip's four launches on a
+// shard's vector, two all-gathers of dot partials per iteration, no basis; the
+// host enqueues chunks of iterations one chunk ahead of the control block it
+// has read, with one wait per chunk.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -55,6 +61,10 @@ struct Shard {
     // workspace
     DBuf<double> V, w, ww, r, rr, bb, t1, t2, xv, bv, partA, partB, H, s, cs, sn, ysm, hist;
     DBuf<double> partC, hcgs;               // CGS2: P x (m+1) x G dot partials, the m+1 coefficients
+    // GG_SOLVE_CG: the control block (a replica per shard) and the paired dot's
+    // partials, P slots of 2 G doubles (r.z's G, then z.z's)
+    DBuf<CgState> cgs;
+    DBuf<double> partR;
     long long hist_cap = 0;
     DBuf<DevState> ds;
     DBuf<int> err;                          // P words (slot p is this shard's)
@@ -69,6 +79,17 @@ struct Shard {
 };
 
 using Get = std::function<double *(Shard &)>;
+using GateOf = std::function<Gate(Shard &)>;
+
+// The read-back of the short-recurrence solves (solve_short_recurrence below):
+// two pinned slots, each [per shard: the control block, kSrStateBytes | its P
+// error words] [the IPC error word], and the event behind each slot's copies
+constexpr size_t kSrStateBytes = (std::max(sizeof(CgState), sizeof(BiState)) + 7) / 8 * 8;
+struct SrPipe {
+    char *slot[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    size_t bytes = 0;
+};
 
 }  // namespace
 
@@ -113,6 +134,8 @@ struct gg_dd {
     int G = 1;
     std::vector<std::unique_ptr<Shard>> sh;
     int m_alloc = -1;
+    bool vec_ok = false;                    // the shards' work vectors are allocated (alloc_vectors)
+    SrPipe sr_pipe;
     bool cgs2 = false;                      // GG_SOLVE_CGS2 for the solve in progress
     int div_mode = GG_DIV_EXACT;            // gg_dd_set_division (the shards' wavefront solves)
     std::vector<double> last_hist;
@@ -324,11 +347,11 @@ Gate gate_of(Shard &s, int gi, int mask)
     return gi >= 0 ? gate_i(s, gi) : (mask ? gate_mask(s, mask) : Gate{});
 }
 
-// z = (LU)^-1 y of the arrow-ordered ILU(0), per shard (module comment of host/dd_setup.cpp)
-void apply_minv(gg_dd *d, int gi, int mask, const Get &in, const Get &out)
+// z = (LU)^-1 y of the arrow-ordered ILU(0), per shard (module comment of host/dd_setup.cpp);
+// gi: the iteration the profile marks count for (< 0: none)
+void apply_minv(gg_dd *d, const GateOf &gate, int gi, const Get &in, const Get &out)
 {
     const long long S0 = d->S0;
-    auto gate = [&](Shard &s) { return gate_of(s, gi, mask); };
     int mk = prof_begin(d, GG_DD_PROF_TRSV_L, gi);
     for (auto &sp : d->sh) {
         Shard &s = *sp;
@@ -384,6 +407,10 @@ void apply_minv(gg_dd *d, int gi, int mask, const Get &in, const Get &out)
         launch_trsv(gate(s), s.UI, s.sepflow ? s.t1.p : s.t2.p, out(s), s.err.p + s.p, d->st);   // x_I
     }
     prof_end(d, mk);
+}
+void apply_minv(gg_dd *d, int gi, int mask, const Get &in, const Get &out)
+{
+    apply_minv(d, [&](Shard &s) { return gate_of(s, gi, mask); }, gi, in, out);
 }
 
 // y = A x (b = null) or y = b - A x: the interior rows reference only their
@@ -484,22 +511,37 @@ void dot(gg_dd *d, int gi, int mask, const Get &a, const Get &b, DBuf<double> Sh
     exchange(d, vec(part), 0, d->G);
 }
 
+// the Pl-long work vectors and the single dots' partials, +0 everywhere: what
+// every method needs (a CG solve allocates these alone, no basis); fresh =
+// false: the existing ones re-zeroed, padding and halo included
+void alloc_vectors(gg_dd *d, bool fresh = true)
+{
+    const long long Pl = d->Pl;
+    for (auto &sp : d->sh) {
+        Shard &s = *sp;
+        for (DBuf<double> *b : {&s.w, &s.ww, &s.r, &s.rr, &s.bb, &s.t1, &s.t2, &s.xv, &s.bv}) {
+            if (fresh) b->alloc(Pl);
+            GG_HIP(hipMemsetAsync(b->p, 0, Pl * sizeof(double), d->st));
+        }
+        for (DBuf<double> *b : {&s.partA, &s.partB}) {
+            if (fresh) b->alloc((size_t)d->P * d->G);
+            GG_HIP(hipMemsetAsync(b->p, 0, (size_t)d->P * d->G * sizeof(double), d->st));
+        }
+        if (!s.ds.p) s.ds.alloc(1);
+        if (!s.err.p) s.err.alloc(d->P);
+    }
+    d->vec_ok = true;
+}
+
 void ensure_workspace(gg_dd *d, int m)
 {
     if (d->m_alloc == m) return;
     const long long Pl = d->Pl;
+    alloc_vectors(d);
     for (auto &sp : d->sh) {
         Shard &s = *sp;
         s.V.alloc((size_t)(m + 1) * Pl);
         GG_HIP(hipMemsetAsync(s.V.p, 0, (size_t)(m + 1) * Pl * sizeof(double), d->st));
-        for (DBuf<double> *b : {&s.w, &s.ww, &s.r, &s.rr, &s.bb, &s.t1, &s.t2, &s.xv, &s.bv}) {
-            b->alloc(Pl);
-            GG_HIP(hipMemsetAsync(b->p, 0, Pl * sizeof(double), d->st));
-        }
-        for (DBuf<double> *b : {&s.partA, &s.partB}) {
-            b->alloc((size_t)d->P * d->G);
-            GG_HIP(hipMemsetAsync(b->p, 0, (size_t)d->P * d->G * sizeof(double), d->st));
-        }
         s.H.alloc((size_t)(m + 1) * m);
         GG_HIP(hipMemsetAsync(s.H.p, 0, (size_t)(m + 1) * m * sizeof(double), d->st));
         // two halves: the first and the second pass's partials (in-kernel
@@ -511,8 +553,6 @@ void ensure_workspace(gg_dd *d, int m)
         s.cs.alloc(m + 1);
         s.sn.alloc(m + 1);
         s.ysm.alloc(m + 1);
-        if (!s.ds.p) s.ds.alloc(1);
-        if (!s.err.p) s.err.alloc(d->P);
     }
     d->m_alloc = m;
 }
@@ -748,6 +788,264 @@ void scatter_out(gg_dd *d, DBuf<double> Shard::*src, double *nat)
     for (auto &sp : d->sh) launch_scatter_idx((sp.get()->*src).p, sp->own_slot.p, sp->own_nat.p, nat, sp->nown, d->st);
 }
 
+// ---- short-recurrence methods on shards (GG_SOLVE_CG; DESIGN.md "Sharded CG") ----
+// short_recurrence.h's solve for shards, written once over a method description:
+// every shard keeps a replica of the method's control block, every vector
+// launch and dot of an iteration is gated on it, and the host enqueues the
+// iterations in chunks, one chunk ahead of the state it has read.  The
+// description M supplies
+//   State                          the control block (kernels.h)
+//   kChunk                         iterations per chunk
+//   control(shard)                 the shard's DBuf<State>
+//   ensure(d)                      its own buffers beside alloc_vectors'
+//   enqueue_start(d)               normb, the initial residual, hist[0], the first direction
+//   enqueue_iterations(d, k0, k1)
+//   zero(d)                        its buffers back to +0 after a breakdown
+//   breakdown(h)                   the message for SR_BREAKDOWN
+// An exchange is not gated: every rank enqueues the same exchanges in the same
+// order whatever the iteration at which the solve ends, so the ranks' ipc_seq
+// and k_dd_spmv_x epochs stay equal.  That rests on one rule: whether another
+// chunk is enqueued is decided from the replicated control block read at a
+// chunk's end and from max_iter alone -- nothing rank-local (a timing, an
+// iteration hint, an error word only this rank holds) may enter it.
+void sr_pipe_begin(gg_dd *d)
+{
+    SrPipe &pp = d->sr_pipe;
+    const size_t bytes = d->sh.size() * (kSrStateBytes + d->P * sizeof(int)) + sizeof(int);
+    if (pp.slot[0] && pp.bytes == bytes) return;
+    for (int k = 0; k < 2; k++) {
+        if (pp.slot[k]) GG_HIP(hipHostFree(pp.slot[k]));
+        pp.slot[k] = nullptr;
+        GG_HIP(hipHostMalloc(reinterpret_cast<void **>(&pp.slot[k]), bytes, hipHostMallocDefault));
+        std::memset(pp.slot[k], 0, bytes);
+        if (!pp.ev[k]) GG_HIP(hipEventCreateWithFlags(&pp.ev[k], hipEventDisableTiming));
+    }
+    pp.bytes = bytes;
+}
+// the shards' control blocks and error words and the IPC error word into the slot, then its event
+template <class M>
+void sr_pipe_post(gg_dd *d, int slot)
+{
+    SrPipe &pp = d->sr_pipe;
+    const size_t per = kSrStateBytes + d->P * sizeof(int);
+    for (size_t k = 0; k < d->sh.size(); k++) {
+        Shard &s = *d->sh[k];
+        GG_HIP(hipMemcpyAsync(pp.slot[slot] + k * per, M::control(s).p, sizeof(typename M::State),
+                              hipMemcpyDeviceToHost, d->st));
+        GG_HIP(hipMemcpyAsync(pp.slot[slot] + k * per + kSrStateBytes, s.err.p, d->P * sizeof(int),
+                              hipMemcpyDeviceToHost, d->st));
+    }
+    if (d->xerr.p)
+        GG_HIP(hipMemcpyAsync(pp.slot[slot] + d->sh.size() * per, d->xerr.p, sizeof(int), hipMemcpyDeviceToHost,
+                              d->st));
+    GG_HIP(hipEventRecord(pp.ev[slot], d->st));
+}
+// waits for the slot: the control block (the replicas must agree bit for bit),
+// *err = the shards' error words OR-ed, *xerr = the IPC error word
+template <class State>
+State sr_pipe_wait(gg_dd *d, int slot, int *err, int *xerr)
+{
+    SrPipe &pp = d->sr_pipe;
+    const size_t per = kSrStateBytes + d->P * sizeof(int);
+    GG_HIP(hipEventSynchronize(pp.ev[slot]));
+    State h0;
+    std::memcpy(&h0, pp.slot[slot], sizeof(State));
+    *err = 0;
+    for (size_t k = 0; k < d->sh.size(); k++) {
+        State h;
+        std::memcpy(&h, pp.slot[slot] + k * per, sizeof(State));
+        GG_REQUIRE(std::memcmp(&h.resid, &h0.resid, sizeof(double)) == 0 && h.done == h0.done && h.it == h0.it,
+                   GG_EINVAL, "dd: shard control blocks diverged");
+        int e[kMaxShards];
+        std::memcpy(e, pp.slot[slot] + k * per + kSrStateBytes, d->P * sizeof(int));
+        for (int q = 0; q < d->P; q++) *err |= e[q];
+    }
+    *xerr = 0;
+    if (d->xerr.p) std::memcpy(xerr, pp.slot[slot] + d->sh.size() * per, sizeof(int));
+    return h0;
+}
+
+template <class M>
+int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+{
+    using State = typename M::State;
+    const int max_iter = opt->max_iter;
+    if (!d->vec_ok) alloc_vectors(d);
+    M::ensure(d);
+    const long long need = (long long)max_iter + 1;
+    for (auto &sp : d->sh)
+        if (need > sp->hist_cap) {
+            sp->hist.alloc(need);
+            sp->hist_cap = need;
+        }
+    sr_pipe_begin(d);
+    d->marks.clear();
+    d->prof_used = 0;
+    gather_in(d, d_b, &Shard::bv);
+    gather_in(d, d_x, &Shard::xv);
+    reset_waves(d);
+    State h0{};
+    h0.tol = opt->tol;
+    h0.max_iter = max_iter;
+    for (auto &sp : d->sh)
+        GG_HIP(hipMemcpyAsync(M::control(*sp).p, &h0, sizeof(State), hipMemcpyHostToDevice, d->st));
+    GG_HIP(hipEventRecord(d->ev0, d->st));
+    M::enqueue_start(d);
+    int next = 0;                                       // first iteration not yet enqueued
+    auto enqueue = [&](int slot) {
+        const int k1 = (int)std::min<long long>((long long)next + M::kChunk, max_iter);
+        M::enqueue_iterations(d, next, k1);
+        next = k1;
+        sr_pipe_post<M>(d, slot);
+    };
+    enqueue(0);
+    enqueue(1);
+    // an error word can end the solve early only where it is the same for
+    // every rank: this process holds every shard, or the communicator is lost
+    // (a peer timed out: every rank sees it).  Otherwise the solve runs to the
+    // end its replicated state gives and check_err below, which gathers the
+    // ranks' words, raises it on every rank alike
+    const bool all_here = d->kind == GG_DD_LOCAL || d->kind == GG_DD_LOOPBACK || d->P == 1;
+    int cur = 0, err = 0, xerr = 0;
+    State h{};
+    while (true) {
+        h = sr_pipe_wait<State>(d, cur, &err, &xerr);       // the one host wait of a chunk
+        if ((xerr & 4) || (all_here && (err & (8 | 1 | 2)))) break;
+        if (h.done || h.it >= max_iter) break;
+        enqueue(cur);
+        cur ^= 1;
+    }
+    {
+        int e2 = 0, x2 = 0;                                 // the chunk behind the last: gated off
+        (void)sr_pipe_wait<State>(d, cur ^ 1, &e2, &x2);
+    }
+    GG_HIP(hipEventRecord(d->ev1, d->st));
+    check_err(d);
+    prof_collect(d, h.it);
+    scatter_out(d, &Shard::xv, d_x);
+    GG_HIP(hipStreamSynchronize(d->st));
+    float ms = 0.f;
+    GG_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+    const long long hist_len = (long long)h.it + 1;
+    d->last_hist.resize(hist_len);
+    GG_HIP(hipMemcpy(d->last_hist.data(), d->sh[0]->hist.p, hist_len * sizeof(double), hipMemcpyDeviceToHost));
+    int ret = GG_NOT_CONVERGED;
+    if (h.done & (SR_CONV | SR_INIT)) ret = GG_OK;
+    else if (h.done & SR_BREAKDOWN) {
+        ret = GG_EBREAKDOWN;
+        set_error(M::breakdown(h));
+        // the scalar may not have been finite: NaN in the vectors' padding would
+        // reach every dot of the next solve on this object
+        alloc_vectors(d, false);
+        M::zero(d);
+        GG_HIP(hipStreamSynchronize(d->st));
+    }
+    if (res) {
+        res->status = ret;
+        res->iters = h.it;
+        res->inner_iters = h.it;
+        res->restarts = 0;
+        res->relres = h.resid;
+        res->solve_ms = ms;
+    }
+    return ret;
+}
+
+// Conjugate gradients (ggmres.h GG_SOLVE_CG, the recurrence of cg.hip's header)
+// on B with M = the sharded ILU(0) apply.  Vectors as cg.hip: r = rr, z = r,
+// p = w, q = ww, x = xv, b = bv.  An iteration: the SpMV with its halo exchange,
+// p.q partials | all-gather of G per shard | x, r update, the apply with its
+// interface exchange, r.z and z.z partials in one pass | ONE all-gather of 2 G
+// per shard | p update (history, control block).
+struct DdCg {
+    using State = CgState;
+    // iterations per chunk (DESIGN.md "Sharded CG"): an iteration is at least
+    // ten launches, so eight of them hide the host's read-back and enqueue many
+    // times over, and a converged solve leaves at most 2 * 8 - 1 iterations of
+    // exchanges -- which are not gated -- and returning launches behind its end
+    static constexpr int kChunk = 8;
+    static DBuf<State> &control(Shard &s) { return s.cgs; }
+    static void ensure(gg_dd *d)
+    {
+        for (auto &sp : d->sh) {
+            Shard &s = *sp;
+            if (!s.cgs.p) s.cgs.alloc(1);
+            if (s.partR.p) continue;
+            s.partR.alloc((size_t)2 * d->P * d->G);
+            GG_HIP(hipMemsetAsync(s.partR.p, 0, (size_t)2 * d->P * d->G * sizeof(double), d->st));
+        }
+    }
+    static void zero(gg_dd *d)
+    {
+        for (auto &sp : d->sh)
+            GG_HIP(hipMemsetAsync(sp->partR.p, 0, (size_t)2 * d->P * d->G * sizeof(double), d->st));
+    }
+    static Gate gate(Shard &s, int k)
+    {
+        Gate g;
+        g.done = &s.cgs.p->done;
+        g.mask = ~0;
+        g.nit = &s.cgs.p->max_iter;
+        g.i = k;
+        return g;
+    }
+    // r.z | z.z partials into the shard's slot, one all-gather, the p update
+    static void pair_and_p(gg_dd *d, int k, bool start)
+    {
+        const long long G2 = 2LL * d->G;
+        for (auto &sp : d->sh) {
+            Shard &s = *sp;
+            launch_cg_rz(start ? Gate{} : gate(s, k), s.rr.p, s.r.p, s.partR.p + s.p * G2, d->G, dot_len(d, s),
+                         d->st);
+        }
+        exchange(d, vec(&Shard::partR), 0, G2);
+        for (auto &sp : d->sh) {
+            Shard &s = *sp;
+            launch_cg_p_r(start ? Gate{} : gate(s, k), k, start, s.cgs.p, s.partR.p, d->P, d->G, s.w.p, s.r.p,
+                          s.hist.p, d->H0, d->st);
+        }
+    }
+    static void enqueue_start(gg_dd *d)
+    {
+        apply_minv(d, -1, 0, vec(&Shard::bv), vec(&Shard::bb));                    // bb = M b
+        dot(d, -1, 0, vec(&Shard::bb), vec(&Shard::bb), &Shard::partA);
+        for (auto &sp : d->sh) launch_normb(sp->partA.p, d->P * d->G, &sp->cgs.p->normb, d->st);
+        resid(d, 0);                                                                // r = b - A x
+        apply_minv(d, -1, 0, vec(&Shard::rr), vec(&Shard::r));                     // z = M r
+        pair_and_p(d, 0, true);                                                     // p = z
+    }
+    static void enqueue_iterations(gg_dd *d, int k0, int k1)
+    {
+        const int NP = d->P * d->G;
+        for (int k = k0; k < k1; k++) {
+            const GateOf gt = [k](Shard &s) { return gate(s, k); };
+            int mk = prof_begin(d, GG_DD_PROF_SPMV, k);
+            spmv_rows(d, vec(&Shard::w), Get{}, vec(&Shard::ww), false, gt);        // q = A p
+            prof_end(d, mk);
+            mk = prof_begin(d, GG_DD_PROF_ORTH, k);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_cg_pq(gt(s), s.w.p, s.ww.p, s.partA.p + (long long)s.p * d->G, d->G, dot_len(d, s), d->st);
+            }
+            exchange(d, vec(&Shard::partA), 0, d->G);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_cg_xr_r(gt(s), k, s.cgs.p, s.partA.p, NP, d->G, s.xv.p, s.w.p, s.rr.p, s.ww.p, d->H0, d->st);
+            }
+            prof_end(d, mk);
+            apply_minv(d, gt, k, vec(&Shard::rr), vec(&Shard::r));                  // z = M r
+            mk = prof_begin(d, GG_DD_PROF_ORTH, k);
+            pair_and_p(d, k, false);
+            prof_end(d, mk);
+        }
+    }
+    static std::string breakdown(const State &h)
+    {
+        return "gg_dd_solve: conjugate gradients broke down at iteration " + std::to_string(h.it) +
+               " (p.Ap or r.Mr not positive: A and M must be symmetric positive definite)";
+    }
+};
+
 int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
 {
     GG_REQUIRE(d->have, GG_ESTATE, "gg_dd_solve: no system (call gg_dd_set_system)");
@@ -755,9 +1053,13 @@ int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, 
     const int m = opt->restart;
     GG_REQUIRE(m >= 1 && m <= 512, GG_EINVAL, "gg_dd_solve: restart must be in [1, 512]");
     GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, "gg_dd_solve: negative max_iter");
-    GG_REQUIRE((opt->flags & ~GG_SOLVE_CGS2) == 0, GG_EINVAL, "gg_dd_solve: unknown flags");
+    // (GG_SOLVE_BICGSTAB is not offered on shards: an unknown flag here)
+    GG_REQUIRE((opt->flags & ~(GG_SOLVE_CGS2 | GG_SOLVE_CG)) == 0, GG_EINVAL, "gg_dd_solve: unknown flags");
+    GG_REQUIRE(opt->flags != (GG_SOLVE_CGS2 | GG_SOLVE_CG), GG_EINVAL,
+               "gg_dd_solve: GG_SOLVE_CG orthogonalizes nothing (GG_SOLVE_CGS2 does not apply)");
     d->cgs2 = (opt->flags & GG_SOLVE_CGS2) != 0;
     set_dev(d);
+    if (opt->flags & GG_SOLVE_CG) return solve_short_recurrence<DdCg>(d, d_b, d_x, opt, res);
     ensure_workspace(d, m);
     const long long need = (long long)opt->max_iter + opt->max_iter / m + 4;
     for (auto &sp : d->sh)
@@ -1033,6 +1335,7 @@ void set_system(gg_dd *d, const Csr &A, int method)
         H = DDShardHost{};
     }
     d->m_alloc = -1;
+    d->vec_ok = false;
     d->have = true;
 }
 
@@ -1171,6 +1474,10 @@ int gg_dd_destroy(gg_dd *d)
         (void)hipFree(d->ipc_area);
     }
     if (d->xk_local) (void)hipFree(d->xk_local);
+    for (int k = 0; k < 2; k++) {
+        if (d->sr_pipe.slot[k]) (void)hipHostFree(d->sr_pipe.slot[k]);
+        if (d->sr_pipe.ev[k]) (void)hipEventDestroy(d->sr_pipe.ev[k]);
+    }
     d->xerr.release();
     if (d->ev0) (void)hipEventDestroy(d->ev0);
     if (d->ev1) (void)hipEventDestroy(d->ev1);
@@ -1349,7 +1656,7 @@ int gg_dd_solve(gg_dd *d, const double *b, double *x, const gg_options *opt, gg_
     stage_nat(d, d->nat_a, b);
     stage_nat(d, d->nat_b, x);
     int rc = solve_dev(d, d->nat_a.p, d->nat_b.p, opt, res);
-    if (rc >= 0) fetch_nat(d, d->nat_b, x);
+    if (rc >= 0 || rc == GG_EBREAKDOWN) fetch_nat(d, d->nat_b, x);       // (a breakdown: the last iterate)
     return rc;
     GG_API_END
 }

@@ -382,6 +382,16 @@ void launch_cg_rz(Gate g, const double *r, const double *z, double *part, int G,
 //   counted): hist[0], resid <= tol: SR_INIT, p = z
 void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, int G, double *p, const double *z,
                  double *hist, long long Ppad, hipStream_t st, Batch bt = {});
+// The sharded solve (dd.hip): a shard's dot covers its dot range and its updates all H0 local
+// slots, so launch_cg_pq and launch_cg_rz run there with Ppad = the dot range and part = the
+// shard's slot of the all-gathered array (G doubles for p . q; 2 G for the pair, r . z's G then
+// z . z's), and these two take every shard's partials, summed shard-major in sum_partials' order:
+//   launch_cg_xr with part = nparts_in = P * G contiguous partials (grid G, Ppad = H0)
+void launch_cg_xr_r(Gate g, int it, CgState *cs, const double *part, int nparts_in, int G, double *x,
+                    const double *p, double *r, const double *q, long long Ppad, hipStream_t st);
+//   launch_cg_p with part = P slots of 2 G doubles, each of the two sums strided over them
+void launch_cg_p_r(Gate g, int it, bool start, CgState *cs, const double *part, int P, int G, double *p,
+                   const double *z, double *hist, long long Ppad, hipStream_t st);
 
 // ---- BiCGStab (GG_SOLVE_BICGSTAB, bicgstab.hip; kernels/short_recurrence.hip) ----
 // Device-side control block of a BiCGStab solve, gated like CgState.  alpha

@@ -25,6 +25,29 @@ namespace {
 // partials, control block,
 // history, the gate's words) blockIdx.y * zs bytes on; the control block is
 // then written by thread 0 of block (0, scenario).  zs = 0: the single solve.
+//
+// The sharded solve (dd.hip "Sharded CG") runs the same kernels on a shard's
+// vector: grid G, the updates over the shard's H0 slots, a dot over its dot
+// range alone (k_cg_pq, k_cg_rz: units = the dot range), its G partials written
+// into the shard's slot of an all-gathered array.  A consumer then sums P * G
+// partials shard-major: k_cg_xr takes the p.q slots, G doubles each and so
+// contiguous, as G = P * G; k_cg_p<START, true> takes the paired dot's slots,
+// 2 G doubles each -- r.z's G, then z.z's -- through sum_partials_sh.
+//
+// Sum of the P * G partials in P slots of `slot` doubles (shard q's G at part +
+// q * slot): sum_partials' order over the values taken shard-major, identical
+// in every block.  slot = G: sum_partials(part, P * G).
+__device__ __forceinline__ double sum_partials_sh(const double *part, int P, int G, long long slot)
+{
+    double v = 0.0;
+    const int n = P * G;
+    for (int k = threadIdx.x; k < n; k += kBlock) {
+        const int q = k / G;
+        v += part[q * slot + (k - q * G)];
+    }
+    return block_sum(v);
+}
+
 __global__ void k_normb(const double *part, int G, double *normb, long long zs = 0)
 {
     part = zp(part, zs, blockIdx.y);
@@ -159,10 +182,11 @@ __global__ __launch_bounds__(kBlock) void k_cg_rz(Gate g, const double *__restri
 // (START: res <= tol, else res < tol), breakdown (not converged and not rzn > 0,
 // NaN included); otherwise p = beta p + z with beta = rzn / rz (START: p = z).
 // it: the iteration's 0-based index (START: the initial residual, nothing counted)
-template <bool START>
+// SH: the sharded solve -- part holds P slots of 2 G doubles (above)
+template <bool START, bool SH = false>
 __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, const double *part, int G,
                                                  double *__restrict__ p, const double *__restrict__ z,
-                                                 double *hist, long long units, long long zs = 0)
+                                                 double *hist, long long units, long long zs = 0, int P = 1)
 {
     if (gated_z(g, zs, blockIdx.y)) return;
     cs = zp(cs, zs, blockIdx.y);
@@ -184,8 +208,8 @@ __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, co
         }
     };
     load();
-    const double rzn = sum_partials(part, G);
-    const double zz = sum_partials(part + G, G);
+    const double rzn = SH ? sum_partials_sh(part, P, G, 2LL * G) : sum_partials(part, G);
+    const double zz = SH ? sum_partials_sh(part + G, P, G, 2LL * G) : sum_partials(part + G, G);
     const double res = sqrt(zz) / cs->normb;
     const bool conv = START ? res <= cs->tol : res < cs->tol;
     const bool brk = !conv && !(rzn > 0.0);
@@ -486,6 +510,18 @@ void launch_cg_p(Gate g, int it, bool start, CgState *cs, const double *part, in
 {
     if (start) k_cg_p<true><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, bt.zs);
     else k_cg_p<false><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, bt.zs);
+}
+// the sharded solve's consumers (dd.hip): nparts_in = P * G contiguous partials; P slots of 2 G
+void launch_cg_xr_r(Gate g, int it, CgState *cs, const double *part, int nparts_in, int G, double *x,
+                    const double *p, double *r, const double *q, long long Ppad, hipStream_t st)
+{
+    k_cg_xr<<<G, kBlock, 0, st>>>(g, it, cs, part, nparts_in, x, p, r, q, Ppad / 2, 0);
+}
+void launch_cg_p_r(Gate g, int it, bool start, CgState *cs, const double *part, int P, int G, double *p,
+                   const double *z, double *hist, long long Ppad, hipStream_t st)
+{
+    if (start) k_cg_p<true, true><<<G, kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, 0, P);
+    else k_cg_p<false, true><<<G, kBlock, 0, st>>>(g, it, cs, part, G, p, z, hist, Ppad / 2, 0, P);
 }
 
 // ---- BiCGStab (bicgstab.hip, bicgstab_batch.hip) -----------------------------------

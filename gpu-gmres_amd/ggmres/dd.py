@@ -1,4 +1,5 @@
-"""Sharded GMRES(m) + ILU(0) over P GPUs (include/ggmres_dd.h).
+"""Sharded GMRES(m) or conjugate gradients + ILU(0) over P GPUs (include/ggmres_dd.h,
+SURVEY.md 8(e)).
 
 DD(nparts, device=0)                    all shards in this process on one GPU
 DD(nparts, rank=r, uid=bytes, device=d) one shard per process (RCCL); uid from
@@ -152,7 +153,10 @@ class DD:
         return out[:ln], G.value
 
     def solve(self, b, x0=None, restart=30, max_iter=3000, tol=1e-10, flags=0):
-        """flags: ggmres.SOLVE_CGS2 for the three-all-gather orthogonalization"""
+        """flags: ggmres.SOLVE_CGS2 for the three-all-gather orthogonalization, or
+        ggmres.SOLVE_CG for conjugate gradients (B and its ILU(0) SPD): ret is then
+        0, 1 or ggmres.EBREAKDOWN -- returned, not raised, with x the last iterate,
+        the history and the counts, as ggmres.Solver.solve does"""
         b = np.ascontiguousarray(b, np.float64)
         x = np.zeros(self.n) if x0 is None else np.array(x0, np.float64, copy=True)
         o = Options(int(restart), int(max_iter), float(tol), int(flags))

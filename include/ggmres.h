@@ -108,7 +108,8 @@ typedef struct gg_options {
  * of the reference's modified Gram-Schmidt (src/gmres.cu:2356-2359): three
  * all-gathers per inner iteration (h, h2, the norm) instead of i + 2.  A
  * different rounding (north_star's 1e-10 history tolerance); the default
- * stays MGS.  gg_solve refuses it (GG_EINVAL). */
+ * stays MGS.  gg_solve refuses it (GG_EINVAL), and so does the sharded solve
+ * together with GG_SOLVE_CG, which orthogonalizes nothing. */
 #define GG_SOLVE_CGS2 0x2
 /* gg_options.flags: solve by left-preconditioned conjugate gradients instead
  * of GMRES(m).  A and the preconditioner M are ASSUMED symmetric positive
@@ -124,8 +125,10 @@ typedef struct gg_options {
  * validated and otherwise ignored.  gg_result: iters = inner_iters = the
  * iterations performed, restarts = 0, relres = the last ||z|| / normb;
  * gg_get_history: the initial value, then one entry per iteration.
- * Accepted by gg_solve, gg_solve_device, gg_solve_device_f32 and the
- * gg_transient* loops (warm start as with GMRES), with GG_PRECOND_NONE, DIAG,
+ * Accepted by gg_solve, gg_solve_device, gg_solve_device_f32, the
+ * gg_transient* loops (warm start as with GMRES) and the sharded
+ * gg_dd_solve / gg_dd_solve_device (ggmres_dd.h: on the arrow-permuted system
+ * with the sharded ILU(0), every communicator), with GG_PRECOND_NONE, DIAG,
  * AINV, ILU0, ILUK or LU (host- or device-factored, any triangular-solve
  * path); GG_EINVAL with GG_PRECOND_SPLIT / USER / USER_SPLIT and in
  * gg_solve_batch* and gg_transient_batch, which define no flags: many
@@ -160,7 +163,8 @@ typedef struct gg_options {
  * gg_solve_device_f32 and the gg_transient* loops, with GG_PRECOND_NONE, DIAG,
  * AINV, ILU0, ILUK or LU on any triangular-solve path and in any division
  * mode; GG_EINVAL together with GG_SOLVE_CG, with GG_PRECOND_SPLIT / USER /
- * USER_SPLIT, in the sharded solve, and in gg_solve_batch* and
+ * USER_SPLIT, in the sharded solve (gg_dd_solve*, which offers GG_SOLVE_CG
+ * alone of the two), and in gg_solve_batch* and
  * gg_transient_batch, which define no flags: many right-hand sides are solved
  * by BiCGStab through entry points of their own,
  * gg_solve_bicgstab_batch_device, gg_solve_bicgstab_batch and

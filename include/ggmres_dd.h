@@ -1,5 +1,6 @@
 /*
- * ggmres_dd.h -- C ABI of the sharded (domain-decomposed) GMRES solve, SURVEY.md 8(e).
+ * ggmres_dd.h -- C ABI of the sharded (domain-decomposed) solve, SURVEY.md 8(e):
+ * GMRES(m), or conjugate gradients (GG_SOLVE_CG, below).
  *
  * Replaces the reference's multi-domain path: partition4 (src/partition3.cpp:122-194,
  * METIS_PartGraphRecursive -> our recursive BFS bisection / contiguous blocks),
@@ -17,6 +18,29 @@
  *     of every triangular solve runs the reference's operations in the
  *     reference's order (LUSolve_ignoreZero, src/SpMV_compute.cpp:92-136):
  *     the operators are bit-identical to the single-GPU solve of B.
+ *
+ * Methods (opt->flags of gg_dd_solve / gg_dd_solve_device; every communicator):
+ *   0              GMRES(m) with the reference's modified Gram-Schmidt;
+ *   GG_SOLVE_CGS2  GMRES(m) with CGS2: three all-gathers per inner iteration;
+ *   GG_SOLVE_CG    ggmres.h's GG_SOLVE_CG exactly, on B with M = the sharded
+ *                  ILU(0) apply (symmetric where B is): no basis, no Hessenberg,
+ *                  two all-gathers of dot partials per iteration whatever its
+ *                  number -- p.q's, and ONE that carries r.z and z.z together.
+ *                  tol, max_iter and restart as there (restart validated in
+ *                  [1, 512], otherwise ignored; no Krylov work space is
+ *                  allocated or touched).  gg_result: iters = inner_iters = the
+ *                  iterations performed, restarts = 0, relres = the last
+ *                  ||z|| / normb; gg_dd_get_history: the initial value, then
+ *                  one entry per iteration.  GG_EBREAKDOWN when p.Ap is not
+ *                  > 0, or r.Mr is not > 0 while the solve has not converged
+ *                  (NaN counts as not > 0): x then holds the last iterate on
+ *                  the rows this process owns, gg_last_error the text, and the
+ *                  object is clean for the next solve.  The host enqueues the
+ *                  iterations in chunks, one chunk ahead of the control block
+ *                  it has read: one host wait per chunk, none per iteration.
+ *   Any other combination is GG_EINVAL: GG_SOLVE_CG with GG_SOLVE_CGS2 (CG
+ *   orthogonalizes nothing), and GG_SOLVE_BICGSTAB, which the sharded solve
+ *   does not offer.
  *
  * Three communicators:
  *   GG_DD_RCCL   one process per GPU (torchrun), shard = rank, RCCL collectives
@@ -128,7 +152,12 @@ int gg_dd_time_exchange(gg_dd *d, long long cnt, int reps, double *avg_us);
  * really ran): the interior rows' + separator rows' SpMV with its halo
  * exchange, the interior L solve, the separator step (interface exchange and
  * separator solves), the interior U solve, the orthogonalization (its
- * exchanges included).  kinds: a mask of (1 << GG_DD_PROF_*). */
+ * exchanges included).  A GG_SOLVE_CG solve accounts its iterations the same
+ * way: SPMV, TRSV_L, SEP and TRSV_U once per iteration, and under
+ * GG_DD_PROF_ORTH -- CG orthogonalizes nothing -- its four launches with their
+ * two all-gathers, as two marks per iteration: p.q partials | all-gather | x, r
+ * update, and r.z, z.z partials | all-gather | p update.
+ * kinds: a mask of (1 << GG_DD_PROF_*). */
 enum gg_dd_prof_kind {
     GG_DD_PROF_SPMV = 0, GG_DD_PROF_TRSV_L = 1, GG_DD_PROF_SEP = 2, GG_DD_PROF_TRSV_U = 3,
     GG_DD_PROF_ORTH = 4, GG_DD_PROF_NKINDS = 5
