@@ -137,6 +137,7 @@ struct gg_dd {
     bool vec_ok = false;                    // the shards' work vectors are allocated (alloc_vectors)
     SrPipe sr_pipe;
     bool cgs2 = false;                      // GG_SOLVE_CGS2 for the solve in progress
+    bool transient_hint = true;             // gg_dd_set_transient_hint (the transient loop's CG steps)
     int div_mode = GG_DIV_EXACT;            // gg_dd_set_division (the shards' wavefront solves)
     std::vector<double> last_hist;
     DBuf<double> nat_a, nat_b;
@@ -807,7 +808,12 @@ void scatter_out(gg_dd *d, DBuf<double> Shard::*src, double *nat)
 // and k_dd_spmv_x epochs stay equal.  That rests on one rule: whether another
 // chunk is enqueued is decided from the replicated control block read at a
 // chunk's end and from max_iter alone -- nothing rank-local (a timing, an
-// iteration hint, an error word only this rank holds) may enter it.
+// iteration count only this rank measured, an error word only this rank holds)
+// may enter it.  The transient loop's first-chunk length keeps the rule: it is
+// the previous step's iteration count as read from the replicated control block
+// (+ 2), and whether the hint applies is a setting every rank must make alike
+// (gg_dd_set_transient_hint), so every rank enqueues the same chunk lengths.
+// The gates make the results independent of the chunk lengths: the same bits.
 void sr_pipe_begin(gg_dd *d)
 {
     SrPipe &pp = d->sr_pipe;
@@ -865,14 +871,17 @@ State sr_pipe_wait(gg_dd *d, int slot, int *err, int *xerr)
     return h0;
 }
 
+// The solve in three parts, so that the transient loop (gg_dd_transient_src below)
+// runs the middle one alone on the state its previous step left in the slots:
+// sr_prepare (buffers), [load: gather_in of b and x], sr_run (the solve on
+// Shard::bv / Shard::xv in place), [store: scatter_out of xv], sr_finish (the
+// history, the status, the clean-up after a breakdown).
 template <class M>
-int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+void sr_prepare(gg_dd *d, const gg_options *opt)
 {
-    using State = typename M::State;
-    const int max_iter = opt->max_iter;
     if (!d->vec_ok) alloc_vectors(d);
     M::ensure(d);
-    const long long need = (long long)max_iter + 1;
+    const long long need = (long long)opt->max_iter + 1;
     for (auto &sp : d->sh)
         if (need > sp->hist_cap) {
             sp->hist.alloc(need);
@@ -881,8 +890,15 @@ int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_op
     sr_pipe_begin(d);
     d->marks.clear();
     d->prof_used = 0;
-    gather_in(d, d_b, &Shard::bv);
-    gather_in(d, d_x, &Shard::xv);
+}
+// first: the first chunk's iterations (M::kChunk outside a transient; inside,
+// the previous step's count + 2 -- a number every rank read from its replica of
+// the control block, so every rank passes the same one and the rule above holds)
+template <class M>
+typename M::State sr_run(gg_dd *d, const gg_options *opt, int first)
+{
+    using State = typename M::State;
+    const int max_iter = opt->max_iter;
     reset_waves(d);
     State h0{};
     h0.tol = opt->tol;
@@ -892,14 +908,14 @@ int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_op
     GG_HIP(hipEventRecord(d->ev0, d->st));
     M::enqueue_start(d);
     int next = 0;                                       // first iteration not yet enqueued
-    auto enqueue = [&](int slot) {
-        const int k1 = (int)std::min<long long>((long long)next + M::kChunk, max_iter);
+    auto enqueue = [&](int slot, int len) {
+        const int k1 = (int)std::min<long long>((long long)next + len, max_iter);
         M::enqueue_iterations(d, next, k1);
         next = k1;
         sr_pipe_post<M>(d, slot);
     };
-    enqueue(0);
-    enqueue(1);
+    enqueue(0, first);
+    enqueue(1, M::kChunk);
     // an error word can end the solve early only where it is the same for
     // every rank: this process holds every shard, or the communicator is lost
     // (a peer timed out: every rank sees it).  Otherwise the solve runs to the
@@ -912,7 +928,7 @@ int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_op
         h = sr_pipe_wait<State>(d, cur, &err, &xerr);       // the one host wait of a chunk
         if ((xerr & 4) || (all_here && (err & (8 | 1 | 2)))) break;
         if (h.done || h.it >= max_iter) break;
-        enqueue(cur);
+        enqueue(cur, M::kChunk);
         cur ^= 1;
     }
     {
@@ -922,13 +938,25 @@ int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_op
     GG_HIP(hipEventRecord(d->ev1, d->st));
     check_err(d);
     prof_collect(d, h.it);
-    scatter_out(d, &Shard::xv, d_x);
+    return h;
+}
+// keep_x (the transient loop): a breakdown's clean-up leaves the last iterate in
+// the real slots of xv -- the state of the next step -- and +0.0 in its padding and
+// halo: through the natural-order scratch nat_a (the rows this process holds out,
+// the re-zeroing, the same rows back in; the transient loop has allocated it)
+void keep_state_begin(gg_dd *d) { scatter_out(d, &Shard::xv, d->nat_a.p); }
+void keep_state_end(gg_dd *d) { gather_in(d, d->nat_a.p, &Shard::xv); }
+template <class M>
+int sr_finish(gg_dd *d, const typename M::State &h, gg_result *res, bool keep_x = false, bool want_hist = true)
+{
     GG_HIP(hipStreamSynchronize(d->st));
     float ms = 0.f;
     GG_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-    const long long hist_len = (long long)h.it + 1;
-    d->last_hist.resize(hist_len);
-    GG_HIP(hipMemcpy(d->last_hist.data(), d->sh[0]->hist.p, hist_len * sizeof(double), hipMemcpyDeviceToHost));
+    if (want_hist) {
+        const long long hist_len = (long long)h.it + 1;
+        d->last_hist.resize(hist_len);
+        GG_HIP(hipMemcpy(d->last_hist.data(), d->sh[0]->hist.p, hist_len * sizeof(double), hipMemcpyDeviceToHost));
+    }
     int ret = GG_NOT_CONVERGED;
     if (h.done & (SR_CONV | SR_INIT)) ret = GG_OK;
     else if (h.done & SR_BREAKDOWN) {
@@ -936,8 +964,10 @@ int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_op
         set_error(M::breakdown(h));
         // the scalar may not have been finite: NaN in the vectors' padding would
         // reach every dot of the next solve on this object
+        if (keep_x) keep_state_begin(d);
         alloc_vectors(d, false);
         M::zero(d);
+        if (keep_x) keep_state_end(d);
         GG_HIP(hipStreamSynchronize(d->st));
     }
     if (res) {
@@ -949,6 +979,17 @@ int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_op
         res->solve_ms = ms;
     }
     return ret;
+}
+
+template <class M>
+int solve_short_recurrence(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+{
+    sr_prepare<M>(d, opt);
+    gather_in(d, d_b, &Shard::bv);
+    gather_in(d, d_x, &Shard::xv);
+    const typename M::State h = sr_run<M>(d, opt, M::kChunk);
+    scatter_out(d, &Shard::xv, d_x);
+    return sr_finish<M>(d, h, res);
 }
 
 // Conjugate gradients (ggmres.h GG_SOLVE_CG, the recurrence of cg.hip's header)
@@ -1046,20 +1087,30 @@ struct DdCg {
     }
 };
 
-int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+// the options every sharded solve takes (gg_dd_solve, and a step of the transient loop)
+void check_options(gg_dd *d, const gg_options *opt, const std::string &who)
 {
-    GG_REQUIRE(d->have, GG_ESTATE, "gg_dd_solve: no system (call gg_dd_set_system)");
-    GG_REQUIRE(opt, GG_EINVAL, "gg_dd_solve: null options");
+    GG_REQUIRE(d->have, GG_ESTATE, who + ": no system (call gg_dd_set_system)");
+    GG_REQUIRE(opt, GG_EINVAL, who + ": null options");
     const int m = opt->restart;
-    GG_REQUIRE(m >= 1 && m <= 512, GG_EINVAL, "gg_dd_solve: restart must be in [1, 512]");
-    GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, "gg_dd_solve: negative max_iter");
+    GG_REQUIRE(m >= 1 && m <= 512, GG_EINVAL, who + ": restart must be in [1, 512]");
+    GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, who + ": negative max_iter");
     // (GG_SOLVE_BICGSTAB is not offered on shards: an unknown flag here)
-    GG_REQUIRE((opt->flags & ~(GG_SOLVE_CGS2 | GG_SOLVE_CG)) == 0, GG_EINVAL, "gg_dd_solve: unknown flags");
+    GG_REQUIRE((opt->flags & ~(GG_SOLVE_CGS2 | GG_SOLVE_CG)) == 0, GG_EINVAL, who + ": unknown flags");
     GG_REQUIRE(opt->flags != (GG_SOLVE_CGS2 | GG_SOLVE_CG), GG_EINVAL,
-               "gg_dd_solve: GG_SOLVE_CG orthogonalizes nothing (GG_SOLVE_CGS2 does not apply)");
-    d->cgs2 = (opt->flags & GG_SOLVE_CGS2) != 0;
-    set_dev(d);
-    if (opt->flags & GG_SOLVE_CG) return solve_short_recurrence<DdCg>(d, d_b, d_x, opt, res);
+               who + ": GG_SOLVE_CG orthogonalizes nothing (GG_SOLVE_CGS2 does not apply)");
+}
+
+// GMRES(m) in the same three parts as the short-recurrence solve above:
+// gmres_prepare, [load], gmres_run on Shard::bv / Shard::xv in place, [store], gmres_finish
+struct GmresEnd {
+    int ret = 1, iters = 0, inner = 0, restarts = 0;
+    long long hist_len = 1;
+    double relres = 0;
+};
+void gmres_prepare(gg_dd *d, const gg_options *opt)
+{
+    const int m = opt->restart;
     ensure_workspace(d, m);
     const long long need = (long long)opt->max_iter + opt->max_iter / m + 4;
     for (auto &sp : d->sh)
@@ -1067,8 +1118,10 @@ int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, 
             sp->hist.alloc(need);
             sp->hist_cap = need;
         }
-    gather_in(d, d_b, &Shard::bv);
-    gather_in(d, d_x, &Shard::xv);
+}
+GmresEnd gmres_run(gg_dd *d, const gg_options *opt)
+{
+    const int m = opt->restart;
     reset_waves(d);
     DevState h{};
     h.tol = opt->tol;
@@ -1080,65 +1133,83 @@ int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, 
     GG_HIP(hipEventRecord(d->ev0, d->st));
     enqueue_init(d);
     h = read_state(d);
-    int ret = 1, iters = 0, inner = 0, restarts = 0;
-    long long hist_len = 1;
-    double relres = h.resid;
+    GmresEnd o;
+    o.relres = h.resid;
     if (h.done & DONE_INIT) {
-        ret = 0;
+        o.ret = 0;
     } else {
         while (true) {
             if (h.j > opt->max_iter) {
-                ret = 1;
-                relres = h.resid;
-                iters = opt->max_iter;
-                hist_len = h.hist_len;
+                o.ret = 1;
+                o.relres = h.resid;
+                o.iters = opt->max_iter;
+                o.hist_len = h.hist_len;
                 break;
             }
-            restarts++;
+            o.restarts++;
             enqueue_cycle(d, m);
             DevState prev = h;
             h = read_state(d);
             check_err(d);
             prof_collect(d, (h.done & DONE_INNER) ? h.conv_i + 1 : h.nit);
             if (h.done & DONE_INNER) {
-                ret = 0;
-                iters = prev.j + h.conv_i;
-                inner += h.conv_i + 1;
-                relres = h.resid;
-                hist_len = h.hist_len + h.conv_i + 1;
+                o.ret = 0;
+                o.iters = prev.j + h.conv_i;
+                o.inner += h.conv_i + 1;
+                o.relres = h.resid;
+                o.hist_len = h.hist_len + h.conv_i + 1;
                 break;
             }
-            inner += h.nit;
+            o.inner += h.nit;
             if (h.done & DONE_RESTART) {
-                ret = 0;
-                iters = h.j;
-                relres = h.resid;
-                hist_len = h.hist_len;
+                o.ret = 0;
+                o.iters = h.j;
+                o.relres = h.resid;
+                o.hist_len = h.hist_len;
                 break;
             }
-            hist_len = h.hist_len;
-            relres = h.resid;
+            o.hist_len = h.hist_len;
+            o.relres = h.resid;
         }
     }
     GG_HIP(hipEventRecord(d->ev1, d->st));
     check_err(d);
-    scatter_out(d, &Shard::xv, d_x);
+    return o;
+}
+int gmres_finish(gg_dd *d, const GmresEnd &o, gg_result *res, bool want_hist = true)
+{
     GG_HIP(hipStreamSynchronize(d->st));
     float ms = 0.f;
     GG_HIP(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-    d->last_hist.resize(hist_len);
-    if (hist_len)
-        GG_HIP(hipMemcpy(d->last_hist.data(), d->sh[0]->hist.p, hist_len * sizeof(double),
-                         hipMemcpyDeviceToHost));
+    if (want_hist) {
+        d->last_hist.resize(o.hist_len);
+        if (o.hist_len)
+            GG_HIP(hipMemcpy(d->last_hist.data(), d->sh[0]->hist.p, o.hist_len * sizeof(double),
+                             hipMemcpyDeviceToHost));
+    }
     if (res) {
-        res->status = ret;
-        res->iters = iters;
-        res->inner_iters = inner;
-        res->restarts = restarts;
-        res->relres = relres;
+        res->status = o.ret;
+        res->iters = o.iters;
+        res->inner_iters = o.inner;
+        res->restarts = o.restarts;
+        res->relres = o.relres;
         res->solve_ms = ms;
     }
-    return ret;
+    return o.ret;
+}
+
+int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+{
+    check_options(d, opt, "gg_dd_solve");
+    d->cgs2 = (opt->flags & GG_SOLVE_CGS2) != 0;
+    set_dev(d);
+    if (opt->flags & GG_SOLVE_CG) return solve_short_recurrence<DdCg>(d, d_b, d_x, opt, res);
+    gmres_prepare(d, opt);
+    gather_in(d, d_b, &Shard::bv);
+    gather_in(d, d_x, &Shard::xv);
+    const GmresEnd o = gmres_run(d, opt);
+    scatter_out(d, &Shard::xv, d_x);
+    return gmres_finish(d, o, res);
 }
 
 int solve_dev(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
@@ -1348,6 +1419,157 @@ void fetch_nat(gg_dd *d, const DBuf<double> &buf, double *h)
 {
     GG_HIP(hipMemcpyAsync(h, buf.p, sizeof(double) * d->n, hipMemcpyDeviceToHost, d->st));
     GG_HIP(hipStreamSynchronize(d->st));
+}
+
+// ---- Sharded transient (gg_dd_transient_src; DESIGN.md "Sharded transient") ----
+// transient_loop of solver.hip on shards: backward Euler, step it solves
+// A x_it = B u(it h) + (C/h) x_{it-1} from x_{it-1}.  The state lives in the
+// shards' slots (Shard::xv) from the one gather_in before step 1 to the one
+// scatter_out after the last step; a step enqueues the source values (one launch
+// per process), the right-hand side in slot order (one launch per shard, xv ->
+// bv), the solve's middle part (sr_run / gmres_run: no load, no store), and the
+// port capture (one launch).  No natural-order vector is touched per step.
+//
+// Tables per call, built on the host from the slot -> row maps.  INVARIANT: every
+// padding slot of [0, H0) holds +0.0 in c (built so here) and in xv (gather_in
+// writes +0.0 there and every update of x adds a multiple of a vector that is
+// +0.0 there; a breakdown's clean-up restores it, sr_finish), so the right-hand
+// side comes out +0.0 on padding, as gather_in would have left it.
+struct TransientShard {
+    DBuf<double> c;                 // C/h in slot order, H0
+    DBuf<int> sptr, sidx;           // the sources of each slot, ascending k (cs_dl_gaxpy's column order)
+};
+
+int transient_dd(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                 const std::vector<int> &kind, const std::vector<int> &dptr, const std::vector<double> &data,
+                 int nport, const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total)
+{
+    // every check before anything is enqueued: every rank refuses alike
+    check_options(d, opt, "gg_dd_transient");
+    GG_REQUIRE(nport == 0 || (port && port_out), GG_EINVAL, "gg_dd_transient: null port arrays");
+    const int n = d->n;
+    for (int k = 0; k < nsrc; k++)
+        GG_REQUIRE(src_node[k] >= 0 && src_node[k] < n, GG_EINVAL, "gg_dd_transient: source node out of range");
+    for (int j = 0; j < nport; j++)
+        GG_REQUIRE(port[j] >= 0 && port[j] < n, GG_EINVAL, "gg_dd_transient: port out of range");
+    set_dev(d);
+    d->cgs2 = (opt->flags & GG_SOLVE_CGS2) != 0;
+    const bool cg = (opt->flags & GG_SOLVE_CG) != 0;
+    const long long H0 = d->H0;
+    // B^T by natural row: the sources of each row in ascending k
+    std::vector<int> nptr(n + 1, 0), nidx(nsrc);
+    for (int k = 0; k < nsrc; k++) nptr[src_node[k] + 1]++;
+    for (int r = 0; r < n; r++) nptr[r + 1] += nptr[r];
+    {
+        std::vector<int> fill(nptr.begin(), nptr.end() - 1);
+        for (int k = 0; k < nsrc; k++) nidx[fill[src_node[k]]++] = k;
+    }
+    // per shard: c and the sources in slot order; where[row] = the first shard of
+    // this process that holds the (permuted) row, and its slot -- a separator row
+    // is read from the replica of the first shard held
+    std::vector<TransientShard> ts(d->sh.size());
+    std::vector<int> where_sh(n, -1);
+    std::vector<long long> where_slot(n, -1);
+    for (size_t k = 0; k < d->sh.size(); k++) {
+        const Shard &s = *d->sh[k];
+        std::vector<double> c(H0, 0.0);                     // +0.0 on padding (the invariant above)
+        std::vector<int> sptr(H0 + 1, 0), sidx;
+        for (long long t = 0; t < H0; t++) {
+            const long long pr = s.slot2perm[t];
+            if (pr >= 0) {
+                const int r = d->q[pr];
+                c[t] = cdiag[r];
+                sidx.insert(sidx.end(), nidx.begin() + nptr[r], nidx.begin() + nptr[r + 1]);
+                if (where_sh[r] < 0) {
+                    where_sh[r] = (int)k;
+                    where_slot[r] = t;
+                }
+            }
+            sptr[t + 1] = (int)sidx.size();
+        }
+        ts[k].c.upload(c, d->st);
+        ts[k].sptr.upload(sptr, d->st);
+        ts[k].sidx.upload(sidx, d->st);
+        GG_HIP(hipStreamSynchronize(d->st));                // the host vectors end here
+    }
+    std::vector<int> psh(std::max(nport, 1), -1);
+    std::vector<long long> pslot(std::max(nport, 1), 0);
+    for (int j = 0; j < nport; j++) {
+        psh[j] = where_sh[port[j]];
+        pslot[j] = std::max<long long>(where_slot[port[j]], 0);
+    }
+    DBuf<int> d_psh, d_kind, d_dptr;
+    DBuf<long long> d_pslot;
+    DBuf<double> d_data, d_u, d_pv;
+    d_psh.upload(psh, d->st);
+    d_pslot.upload(pslot, d->st);
+    d_kind.upload(kind, d->st);
+    d_dptr.upload(dptr, d->st);
+    d_data.upload(data, d->st);                             // (no sources: one element, nothing copied)
+    d_u.alloc(std::max(nsrc, 1));
+    const size_t npv = (size_t)std::max(nport, 1) * (nsteps + 1);
+    d_pv.alloc(npv);
+    // the hint's switch (gg_dd_set_transient_hint): every rank must set it alike
+    const bool use_hint = d->transient_hint;
+    stage_nat(d, d->nat_b, x);
+    if (d->nat_a.n < (size_t)std::max(n, 1)) d->nat_a.alloc(std::max(n, 1));   // keep_state_*'s scratch
+    int total = 0, status = GG_OK;
+    auto run = [&]() {
+        total = 0;
+        status = GG_OK;
+        GG_HIP(hipMemsetAsync(d_pv.p, 0, npv * sizeof(double), d->st));
+        if (cg) sr_prepare<DdCg>(d, opt);
+        else gmres_prepare(d, opt);
+        gather_in(d, d->nat_b.p, &Shard::xv);
+        ShardPtrs xs{};
+        for (size_t k = 0; k < d->sh.size(); k++) xs.p[k] = d->sh[k]->xv.p;
+        launch_dd_ports(nport, d_psh.p, d_pslot.p, xs, d_pv.p, d->st);
+        int hint = 0;
+        for (int it = 1; it <= nsteps; it++) {
+            launch_sources(nsrc, d_kind.p, d_dptr.p, d_data.p, it, h, d_u.p, d->st);
+            for (size_t k = 0; k < d->sh.size(); k++) {
+                Shard &s = *d->sh[k];
+                launch_dd_transient_rhs(ts[k].sptr.p, ts[k].sidx.p, d_u.p, ts[k].c.p, s.xv.p, s.bv.p, H0, d->st);
+            }
+            gg_result r{};
+            int rc;
+            const bool last = it == nsteps;                 // gg_dd_get_history: the last step's
+            if (cg) {
+                const CgState e = sr_run<DdCg>(d, opt, hint > 0 ? hint + 2 : DdCg::kChunk);
+                rc = sr_finish<DdCg>(d, e, &r, true, last);
+            } else {
+                rc = gmres_finish(d, gmres_run(d, opt), &r, last);
+            }
+            if (rc != GG_OK) status = rc;
+            total += r.iters;
+            hint = use_hint && rc >= 0 ? r.iters : 0;
+            launch_dd_ports(nport, d_psh.p, d_pslot.p, xs, d_pv.p + (size_t)it * nport, d->st);
+        }
+        scatter_out(d, &Shard::xv, d->nat_b.p);
+    };
+    for (int attempt = 0;; attempt++) {
+        try {
+            run();
+            break;
+        } catch (Fallback &f) {
+            // as solve_dev: the triangles' forms are changed and the work repeated --
+            // here the whole loop, from the initial state nat_b still holds
+            if (attempt >= 2) throw Error{GG_EHIP, "gg_dd_transient: fallbacks exhausted"};
+            apply_fallback(d, f);
+        }
+    }
+    if (nport) {
+        std::vector<double> pv(npv);
+        GG_HIP(hipMemcpyAsync(pv.data(), d_pv.p, npv * sizeof(double), hipMemcpyDeviceToHost, d->st));
+        GG_HIP(hipStreamSynchronize(d->st));
+        for (int j = 0; j < nport; j++) {
+            if (psh[j] < 0) continue;                       // not held: the row is left untouched
+            for (int it = 0; it <= nsteps; it++) port_out[(size_t)j * (nsteps + 1) + it] = pv[(size_t)it * nport + j];
+        }
+    }
+    fetch_nat(d, d->nat_b, x);
+    *iters_total = total;
+    return status;
 }
 
 }  // namespace
@@ -1659,6 +1881,45 @@ int gg_dd_solve(gg_dd *d, const double *b, double *x, const gg_options *opt, gg_
     if (rc >= 0 || rc == GG_EBREAKDOWN) fetch_nat(d, d->nat_b, x);       // (a breakdown: the last iterate)
     return rc;
     GG_API_END
+}
+
+int gg_dd_transient_src(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                        const int *src_kind, const int *src_ptr, const double *src_data, int nport,
+                        const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total)
+{
+    GG_API_BEGIN
+    GG_REQUIRE(d && opt && x && cdiag && iters_total, GG_EINVAL, "null argument");
+    GG_REQUIRE(nsteps >= 0 && nsrc >= 0 && nport >= 0, GG_EINVAL, "negative count");
+    GG_REQUIRE(nsrc == 0 || src_node, GG_EINVAL, "null source arrays");
+    std::vector<int> kind, dptr;
+    std::vector<double> data;
+    source_tables(nsrc, src_kind, src_ptr, src_data, kind, dptr, data);
+    return transient_dd(d, nsteps, h, cdiag, nsrc, src_node, kind, dptr, data, nport, port, x, opt, port_out,
+                        iters_total);
+    GG_API_END
+}
+
+int gg_dd_transient(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                    const double *pulse, int nport, const int *port, double *x, const gg_options *opt,
+                    double *port_out, int *iters_total)
+{
+    GG_API_BEGIN
+    GG_REQUIRE(d && opt && x && cdiag && iters_total, GG_EINVAL, "null argument");
+    GG_REQUIRE(nsteps >= 0 && nsrc >= 0 && nport >= 0, GG_EINVAL, "negative count");
+    GG_REQUIRE(nsrc == 0 || (src_node && pulse), GG_EINVAL, "null source arrays");
+    std::vector<int> kind(std::max(nsrc, 1), GG_SRC_PULSE), dptr(nsrc + 1);
+    for (int k = 0; k <= nsrc; k++) dptr[k] = 7 * k;
+    std::vector<double> data(pulse, pulse + (size_t)7 * nsrc);
+    return transient_dd(d, nsteps, h, cdiag, nsrc, src_node, kind, dptr, data, nport, port, x, opt, port_out,
+                        iters_total);
+    GG_API_END
+}
+
+int gg_dd_set_transient_hint(gg_dd *d, int on)
+{
+    if (!d) return GG_EINVAL;
+    d->transient_hint = on != 0;
+    return GG_OK;
 }
 
 int gg_dd_get_history(gg_dd *d, double *out, int cap)

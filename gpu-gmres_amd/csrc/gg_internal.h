@@ -427,7 +427,12 @@ void build_tri(DevTri &T, const CanonTri &C, const Wave2D *wl, const std::vector
 // block (detect_border2d); exact division only (the tail's flow kernel divides)
 void build_tri_bordered(DevTri &T, const CanonTri &C, const CanonTri &Cg, const Wave2D &wl, hipStream_t st);
 long long round_up(long long a, long long b);
+// validated device tables of a gg_src_kind source list (solver.hip; gg_transient_src,
+// gg_transient_mna and dd.hip's gg_dd_transient_src share the check): kind per source,
+// dptr its parameters' range in data (GG_EINVAL on an unknown kind or a wrong length)
+void source_tables(int nsrc, const int *src_kind, const int *src_ptr, const double *src_data,
+                   std::vector<int> &kind, std::vector<int> &dptr, std::vector<double> &data);
 
-struct DevState;   // device-side GMRES control block (kernels.h)
+struct DevState;  // device-side GMRES control block (kernels.h)
 
 }  // namespace gg

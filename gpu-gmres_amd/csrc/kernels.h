@@ -79,6 +79,9 @@ void launch_transient_step_csr(int n, int nsrc, const int *kind, const int *dptr
                                double h, double *u, const int *bp, const int *bi, const double *bv,
                                const int *rp, const int *ri, const double *rv, const double *x, double *w,
                                hipStream_t st);
+// u = sources(it*h) alone (k_sources; the sharded transient loop forms its right-hand side per shard)
+void launch_sources(int nsrc, const int *kind, const int *dptr, const double *data, int it, double h, double *u,
+                    hipStream_t st);
 void launch_gather_ports(int nport, const int *port, const double *x, double *out, hipStream_t st);
 // tap statistics: mode 0 seed (max = min = sum = x[tap]), 1 update, 2 finish (sum /= npts)
 void launch_taps(int ntap, const int *tap, const double *x, double *mx, double *mn, double *sm, int mode,
@@ -123,6 +126,15 @@ void launch_sep_flow(Gate g, int ntask, const int4 *tasks, const int *rows, cons
 struct ShardPtrs { double *p[kMaxShards]; };
 // every shard's slot (b.p[s] + off + s*cnt, cnt doubles) copied to every other shard
 void launch_allgather_local(const ShardPtrs &b, int P, long long off, long long cnt, hipStream_t st);
+// the sharded transient loop's step (kernels/dd_transient.hip), on one shard's slots [0, H0):
+// b[t] = B u + (C/h) x with k_transient_rhs's operations per slot -- sptr (H0 + 1) / sidx the
+// sources of each slot in ascending k, c the slot-ordered C/h (+0.0 on padding)
+void launch_dd_transient_rhs(const int *sptr, const int *sidx, const double *u, const double *c, const double *x,
+                             double *b, long long H0, hipStream_t st);
+// out[j] = xv.p[psh[j]][pslot[j]] for the ports this process holds (psh[j] >= 0: the index
+// into xv of the shard it is read from); the others keep their value
+void launch_dd_ports(int nport, const int *psh, const long long *pslot, const ShardPtrs &xv, double *out,
+                     hipStream_t st);
 // The interface exchange with its gather in the same launch (the SpMV halo and
 // the separator step's interface values): shard s's slot is formed from its
 // own vector, b.p[s][gi.p[s][e]] (-1: 0), and stored into every shard's slot s

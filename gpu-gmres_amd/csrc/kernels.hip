@@ -2432,11 +2432,16 @@ void launch_fill_u64(unsigned long long *p, long long n, unsigned long long v, h
 {
     k_fill_u64<<<dim3(blocks_for(n, kBlock, 4096), bt.nsc), kBlock, 0, st>>>(p, n, v, bt.zs);
 }
+void launch_sources(int nsrc, const int *kind, const int *dptr, const double *data, int it, double h, double *u,
+                    hipStream_t st)
+{
+    if (nsrc > 0) k_sources<<<(nsrc + kBlock - 1) / kBlock, kBlock, 0, st>>>(nsrc, kind, dptr, data, it, h, u);
+}
 void launch_transient_step(int n, int nsrc, const int *kind, const int *dptr, const double *data, int it,
                            double h, double *u, const int *src_ptr, const int *src_idx, const double *cdiag,
                            const double *x, double *w, hipStream_t st)
 {
-    if (nsrc > 0) k_sources<<<(nsrc + kBlock - 1) / kBlock, kBlock, 0, st>>>(nsrc, kind, dptr, data, it, h, u);
+    launch_sources(nsrc, kind, dptr, data, it, h, u, st);
     if (n > 0)
         k_transient_rhs<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(n, src_ptr, src_idx, u, cdiag, x, w);
 }

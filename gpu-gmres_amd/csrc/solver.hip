@@ -1708,6 +1708,27 @@ int solve_one(gg_solver *s, const double *d_b, double *d_x, const gg_options *op
     return solve_device(s, d_b, d_x, opt, res);
 }
 UnitMap solver_unit_map(const gg_solver *s) { return unit_map(s); }
+
+// validated device tables of a gg_src_kind source list (gg_internal.h)
+void source_tables(int nsrc, const int *src_kind, const int *src_ptr, const double *src_data,
+                   std::vector<int> &kind, std::vector<int> &dptr, std::vector<double> &data)
+{
+    GG_REQUIRE(nsrc == 0 || (src_kind && src_ptr && src_data), GG_EINVAL, "null source arrays");
+    kind.assign(std::max(nsrc, 1), GG_SRC_DC);
+    dptr.assign(nsrc + 1, 0);
+    for (int k = 0; k < nsrc; k++) {
+        const int len = src_ptr[k + 1] - src_ptr[k];
+        GG_REQUIRE(src_ptr[k] >= 0 && len >= 0, GG_EINVAL, "transient: bad src_ptr");
+        const int need = src_kind[k] == GG_SRC_DC ? 1 : src_kind[k] == GG_SRC_PULSE ? 7 : -1;
+        GG_REQUIRE(src_kind[k] == GG_SRC_DC || src_kind[k] == GG_SRC_PULSE || src_kind[k] == GG_SRC_PWL,
+                   GG_EINVAL, "transient: unknown source kind");
+        GG_REQUIRE(need < 0 ? (len >= 2 && len % 2 == 0) : len == need, GG_EINVAL,
+                   "transient: DC takes 1 value, PULSE 7, PWL (time, value) pairs");
+        kind[k] = src_kind[k];
+        dptr[k + 1] = src_ptr[k + 1] - src_ptr[0];
+    }
+    data.assign(src_data + (nsrc ? src_ptr[0] : 0), src_data + (nsrc ? src_ptr[nsrc] : 0));
+}
 }  // namespace gg
 
 // ======================================================================= C ABI
@@ -2512,27 +2533,6 @@ int gg_transient_get_taps(gg_solver *s, double *max_v, double *min_v, double *av
     }
     return GG_OK;
     GG_API_END
-}
-
-// validated device tables of a gg_src_kind source list
-static void source_tables(int nsrc, const int *src_kind, const int *src_ptr, const double *src_data,
-                          std::vector<int> &kind, std::vector<int> &dptr, std::vector<double> &data)
-{
-    GG_REQUIRE(nsrc == 0 || (src_kind && src_ptr && src_data), GG_EINVAL, "null source arrays");
-    kind.assign(std::max(nsrc, 1), GG_SRC_DC);
-    dptr.assign(nsrc + 1, 0);
-    for (int k = 0; k < nsrc; k++) {
-        const int len = src_ptr[k + 1] - src_ptr[k];
-        GG_REQUIRE(src_ptr[k] >= 0 && len >= 0, GG_EINVAL, "transient: bad src_ptr");
-        const int need = src_kind[k] == GG_SRC_DC ? 1 : src_kind[k] == GG_SRC_PULSE ? 7 : -1;
-        GG_REQUIRE(src_kind[k] == GG_SRC_DC || src_kind[k] == GG_SRC_PULSE || src_kind[k] == GG_SRC_PWL,
-                   GG_EINVAL, "transient: unknown source kind");
-        GG_REQUIRE(need < 0 ? (len >= 2 && len % 2 == 0) : len == need, GG_EINVAL,
-                   "transient: DC takes 1 value, PULSE 7, PWL (time, value) pairs");
-        kind[k] = src_kind[k];
-        dptr[k + 1] = src_ptr[k + 1] - src_ptr[0];
-    }
-    data.assign(src_data + (nsrc ? src_ptr[0] : 0), src_data + (nsrc ? src_ptr[nsrc] : 0));
 }
 
 int gg_transient_src(gg_solver *s, int nsteps, double h, const double *cdiag, int nsrc,

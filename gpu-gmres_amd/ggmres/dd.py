@@ -13,6 +13,7 @@ DD(nparts, rank=r, comm="loopback")     timing only: shard r alone, every exchan
                                         fixed iteration count: the values are not the system's)
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -30,7 +31,7 @@ EXPORTS = ["gg_dd_unique_id", "gg_dd_create", "gg_dd_destroy", "gg_dd_comm_ranks
            "gg_dd_ipc_handle", "gg_dd_ipc_connect",
            "gg_dd_set_system", "gg_dd_info", "gg_dd_xk_active",
            "gg_dd_perm", "gg_dd_dot_layout", "gg_dd_solve", "gg_dd_solve_device",
-           "gg_dd_get_history", "gg_dd_spmv", "gg_dd_precond_apply", "gg_dd_set_division",
+           "gg_dd_transient_src", "gg_dd_transient", "gg_dd_set_transient_hint", "gg_dd_get_history", "gg_dd_spmv", "gg_dd_precond_apply", "gg_dd_set_division",
            "gg_dd_time_exchange", "gg_dd_profile_enable", "gg_dd_profile_reset", "gg_dd_profile_get",
            "gg_dd_bytes"]
 # gg_dd_prof_kind (ggmres_dd.h)
@@ -58,6 +59,13 @@ def _lib():
         L.gg_dd_solve.argtypes = [_VP, _D, _D, ctypes.POINTER(Options), ctypes.POINTER(Result)]
         L.gg_dd_solve_device.argtypes = [_VP, _VP, _VP, ctypes.POINTER(Options),
                                          ctypes.POINTER(Result)]
+        L.gg_dd_transient_src.argtypes = [_VP, ctypes.c_int, ctypes.c_double, _D, ctypes.c_int, _I, _I, _I, _D,
+                                          ctypes.c_int, _VP, _D, ctypes.POINTER(Options), _VP,
+                                          ctypes.POINTER(ctypes.c_int)]
+        L.gg_dd_transient.argtypes = [_VP, ctypes.c_int, ctypes.c_double, _D, ctypes.c_int, _I, _D,
+                                      ctypes.c_int, _VP, _D, ctypes.POINTER(Options), _VP,
+                                      ctypes.POINTER(ctypes.c_int)]
+        L.gg_dd_set_transient_hint.argtypes = [_VP, ctypes.c_int]
         L.gg_dd_get_history.argtypes = [_VP, _VP, ctypes.c_int]
         L.gg_dd_spmv.argtypes = [_VP, _D, _D]
         L.gg_dd_precond_apply.argtypes = [_VP, _D, _D]
@@ -172,6 +180,69 @@ class DD:
                                               ctypes.byref(r)), allow_nc=True)
         return dict(ret=rc, iters=r.iters, inner=r.inner_iters, restarts=r.restarts,
                     relres=r.relres, solve_ms=r.solve_ms)
+
+    def _transient_io(self, nsteps, ports, x0, x_fill, port_fill):
+        """the in/out state, the port array (preset to port_fill) and the rows of x
+        this process writes back (x_fill given: asked of gg_dd_spmv, which writes
+        the same rows -- x itself is the C entry point's input, so it cannot be preset)"""
+        # the hint's switch, read at every call: GG_DD_TRANSIENT_HINT=0 turns it off
+        off = os.environ.get("GG_DD_TRANSIENT_HINT", "")[:1] == "0"
+        _check(_lib().gg_dd_set_transient_hint(self.h, 0 if off else 1))
+        x = np.array(x0, np.float64, copy=True)
+        ports = np.ascontiguousarray(ports, np.int32)
+        pv = np.full(max(len(ports), 1) * (nsteps + 1), 0.0 if port_fill is None else float(port_fill))
+        own = None
+        if x_fill is not None:
+            own = ~np.isnan(self.spmv(np.zeros(self.n), np.full(self.n, np.nan)))
+        return x, ports, pv, own
+
+    def _transient_out(self, rc, nsteps, ports, x, pv, own, x_fill, tot):
+        if own is not None:
+            x = np.where(own, x, float(x_fill))
+        return dict(ret=rc, x=x, ports=pv[: len(ports) * (nsteps + 1)].reshape(len(ports), nsteps + 1),
+                    iters_total=tot.value)
+
+    def transient_src(self, nsteps, h, cdiag, src_node, sources, ports, x0, restart=32, max_iter=10000,
+                      tol=1e-7, flags=0, x_fill=None, port_fill=None):
+        """gg_dd_transient_src: the backward-Euler loop over the shards, the state in
+        their slots between the steps; sources = [(kind, params), ...] (ggmres.SRC_DC
+        / SRC_PULSE / SRC_PWL), flags 0, ggmres.SOLVE_CGS2 or ggmres.SOLVE_CG.
+        Returns dict(ret, x, ports [nport, nsteps+1], iters_total); ret is GG_OK or
+        the status of the last step that was not (1, ggmres.EBREAKDOWN: returned,
+        not raised).  port_fill presets the port array and x_fill stands in the
+        rows of x this process does not hold (e.g. NaN), so a rank sees what it wrote.
+        Environment GG_DD_TRANSIENT_HINT=0, read at every call (set it alike on every
+        rank): the CG steps take no hint (gg_dd_set_transient_hint)."""
+        x, ports, pv, own = self._transient_io(nsteps, ports, x0, x_fill, port_fill)
+        src_node = np.ascontiguousarray(src_node, np.int32)
+        kind = np.array([k for k, _ in sources], np.int32)
+        ptr = np.zeros(len(sources) + 1, np.int32)
+        ptr[1:] = np.cumsum([len(q) for _, q in sources])
+        data = np.concatenate([np.asarray(q, np.float64) for _, q in sources]) if sources else np.zeros(1)
+        tot = ctypes.c_int()
+        o = Options(int(restart), int(max_iter), float(tol), int(flags))
+        one = np.zeros(1, np.int32)
+        rc = _check(_lib().gg_dd_transient_src(
+            self.h, int(nsteps), float(h), np.ascontiguousarray(cdiag, np.float64), len(src_node),
+            src_node if len(src_node) else one, kind if len(kind) else one, ptr, data, len(ports),
+            ports.ctypes.data if len(ports) else None, x, ctypes.byref(o),
+            pv.ctypes.data if len(ports) else None, ctypes.byref(tot)), allow_nc=True)
+        return self._transient_out(rc, nsteps, ports, x, pv, own, x_fill, tot)
+
+    def transient(self, nsteps, h, cdiag, src_node, pulse, ports, x0, restart=32, max_iter=10000,
+                  tol=1e-7, flags=0, x_fill=None, port_fill=None):
+        """gg_dd_transient: transient_src with PULSE rows pulse[nsrc, 7]"""
+        x, ports, pv, own = self._transient_io(nsteps, ports, x0, x_fill, port_fill)
+        src_node = np.ascontiguousarray(src_node, np.int32)
+        pulse = np.ascontiguousarray(pulse, np.float64).reshape(-1)
+        tot = ctypes.c_int()
+        o = Options(int(restart), int(max_iter), float(tol), int(flags))
+        rc = _check(_lib().gg_dd_transient(
+            self.h, int(nsteps), float(h), np.ascontiguousarray(cdiag, np.float64), len(src_node),
+            src_node if len(src_node) else np.zeros(1, np.int32), pulse if pulse.size else np.zeros(7),
+            len(ports), ports.ctypes.data if len(ports) else None, x, ctypes.byref(o),
+            pv.ctypes.data if len(ports) else None, ctypes.byref(tot)), allow_nc=True)
+        return self._transient_out(rc, nsteps, ports, x, pv, own, x_fill, tot)
 
     def history(self):
         n = _lib().gg_dd_get_history(self.h, None, 0)

@@ -438,7 +438,9 @@ int gg_transient(gg_solver *s, int nsteps, double h, const double *cdiag, int ns
  *                 before t0 the value is v0, where the reference reads v[-1]) */
 enum gg_src_kind { GG_SRC_DC = 0, GG_SRC_PULSE = 1, GG_SRC_PWL = 2 };
 /* gg_transient with any mix of sources: source k at node src_node[k], kind
- * src_kind[k], parameters src_data[src_ptr[k] .. src_ptr[k+1]) */
+ * src_kind[k], parameters src_data[src_ptr[k] .. src_ptr[k+1]).  The same loop
+ * over the shards of a gg_dd object: gg_dd_transient_src / gg_dd_transient
+ * (ggmres_dd.h). */
 int gg_transient_src(gg_solver *s, int nsteps, double h, const double *cdiag, int nsrc,
                      const int *src_node, const int *src_kind, const int *src_ptr, const double *src_data,
                      int nport, const int *port, double *x, const gg_options *opt, double *port_out,

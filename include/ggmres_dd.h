@@ -136,6 +136,57 @@ int gg_dd_solve_device(gg_dd *d, const double *d_b, double *d_x, const gg_option
                        gg_result *res);
 int gg_dd_get_history(gg_dd *d, double *out, int cap);
 
+/* The sharded backward-Euler transient loop: gg_transient_src of ggmres.h on the
+ * system given to gg_dd_set_system (A = G + C/h; cdiag = C/h), over every
+ * communicator (GG_DD_LOOPBACK: timing only, as for the solve).  Step it =
+ * 1..nsteps solves A x_it = B u(it h) + (C/h) x_{it-1}, warm-started from
+ * x_{it-1}: B the sources' incidence matrix (src_node), u their DC / PULSE / PWL
+ * values (src_kind / src_ptr / src_data as gg_transient_src validates them).
+ * The state stays in the shards' slots between the steps: x is gathered in once
+ * before step 1 and scattered out once after the last step, the right-hand side
+ * is formed on the device in slot order with the natural-order kernel's
+ * operations per row (the same bits as w = B u + (C/h) x formed on the host in
+ * the reference's order and passed to gg_dd_solve with x as the start), and the
+ * ports are captured on the device.
+ *   Arrays: host arrays, natural order, identical on every rank.  x is the
+ *   initial state in, the final state out: a process writes the rows it holds,
+ *   as gg_dd_solve.  port_out[j*(nsteps+1) + it], column 0 = the initial x: a
+ *   process writes the rows of the ports it holds and leaves the others
+ *   untouched (GG_DD_LOCAL: all of them; a separator port is held by every
+ *   process); nport = 0: port and port_out may be NULL.  *iters_total = the sum
+ *   of the steps' iteration counts, identical on every rank.
+ *   Methods: opt->flags 0, GG_SOLVE_CGS2 or GG_SOLVE_CG, every other combination
+ *   GG_EINVAL, exactly as gg_dd_solve; restart, max_iter and tol apply per step.
+ *   A GG_SOLVE_CG step's first chunk of iterations is the previous step's count
+ *   + 2 whenever that step returned a status >= 0 -- a count read from the
+ *   replicated control block, the same on every rank; the results do not depend
+ *   on it.  gg_dd_set_transient_hint(d, 0) (every rank alike) enqueues every
+ *   step as gg_dd_solve does, for A/B runs; the Python binding makes that call
+ *   from the environment word GG_DD_TRANSIENT_HINT=0, read at every transient
+ *   call.  The GMRES steps run whole cycles.
+ *   Returns GG_OK, or the status of the last step that did not return GG_OK: a
+ *   step that exhausts max_iter (1) or breaks down (GG_EBREAKDOWN) does not stop
+ *   the loop; after a CG breakdown x keeps the step's last iterate and the
+ *   object is clean for the next step.  Every argument is checked before
+ *   anything is enqueued, so every rank refuses alike: GG_EINVAL for null
+ *   arguments, negative counts, a source node or port outside [0, n), a source
+ *   kind or parameter length gg_transient_src refuses; GG_ESTATE before
+ *   gg_dd_set_system.  gg_dd_get_history afterwards: the last step's history.
+ * gg_dd_transient: the all-PULSE form (pulse[7 * k ..]: vlo, vhi, td, tr, tf, tw,
+ * tp), as gg_transient is over gg_transient_src.
+ * Not offered on shards: tap statistics (gg_transient_set_taps), the general MNA
+ * form (gg_transient_mna) and a many-scenario batch. */
+int gg_dd_transient_src(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
+                        const int *src_node, const int *src_kind, const int *src_ptr,
+                        const double *src_data, int nport, const int *port, double *x,
+                        const gg_options *opt, double *port_out, int *iters_total);
+int gg_dd_transient(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
+                    const int *src_node, const double *pulse, int nport, const int *port,
+                    double *x, const gg_options *opt, double *port_out, int *iters_total);
+/* on = 0: the CG steps of the following gg_dd_transient* calls take no hint
+ * (default 1); set it alike on every rank */
+int gg_dd_set_transient_hint(gg_dd *d, int on);
+
 /* single operators (host vectors, natural order) for parity tests */
 int gg_dd_spmv(gg_dd *d, const double *x, double *y);
 int gg_dd_precond_apply(gg_dd *d, const double *in, double *out);
