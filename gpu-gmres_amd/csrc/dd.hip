@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -65,6 +66,11 @@ struct Shard {
     // partials, P slots of 2 G doubles (r.z's G, then z.z's)
     DBuf<CgState> cgs;
     DBuf<double> partR;
+    // gg_dd_solve_bicgstab: the control block, the shadow residual, t, the SpMV
+    // output M is applied to, and the second paired dot's partials (r.r's G,
+    // then rt.r's, per slot); the first pair (t.s, t.t) takes partR
+    DBuf<BiState> bis;
+    DBuf<double> bi_rt, bi_t, bi_q, partRR;
     long long hist_cap = 0;
     DBuf<DevState> ds;
     DBuf<int> err;                          // P words (slot p is this shard's)
@@ -137,7 +143,7 @@ struct gg_dd {
     bool vec_ok = false;                    // the shards' work vectors are allocated (alloc_vectors)
     SrPipe sr_pipe;
     bool cgs2 = false;                      // GG_SOLVE_CGS2 for the solve in progress
-    bool transient_hint = true;             // gg_dd_set_transient_hint (the transient loop's CG steps)
+    bool transient_hint = true;             // gg_dd_set_transient_hint (the transient loop's CG and BiCGStab steps)
     int div_mode = GG_DIV_EXACT;            // gg_dd_set_division (the shards' wavefront solves)
     std::vector<double> last_hist;
     DBuf<double> nat_a, nat_b;
@@ -789,7 +795,8 @@ void scatter_out(gg_dd *d, DBuf<double> Shard::*src, double *nat)
     for (auto &sp : d->sh) launch_scatter_idx((sp.get()->*src).p, sp->own_slot.p, sp->own_nat.p, nat, sp->nown, d->st);
 }
 
-// ---- short-recurrence methods on shards (GG_SOLVE_CG; DESIGN.md "Sharded CG") ----
+// ---- short-recurrence methods on shards (GG_SOLVE_CG, gg_dd_solve_bicgstab; DESIGN.md
+// "Sharded CG", "Sharded BiCGStab") ----
 // short_recurrence.h's solve for shards, written once over a method description:
 // every shard keeps a replica of the method's control block, every vector
 // launch and dot of an iteration is gated on it, and the host enqueues the
@@ -1087,6 +1094,141 @@ struct DdCg {
     }
 };
 
+// Stabilized biconjugate gradients (gg_dd_solve_bicgstab; the recurrence of
+// bicgstab.hip's header; DESIGN.md "Sharded BiCGStab") on B with M = the sharded
+// ILU(0) apply.  Vectors as bicgstab.hip: r (and s in its place) = rr, p = w,
+// v = ww, x = xv, b = bv; rt, t and the SpMV output q are this method's own.
+// An iteration: SpMV, apply, rt.v partials | all-gather of G | s; SpMV, apply,
+// t.s and t.t partials | ONE all-gather of 2 G | x, r update with the partials
+// of r.r and rt.r | ONE all-gather of 2 G | p update (history, control block).
+// The two pairs go through two arrays: k_bi_xr reads every slot of partR in
+// every block while it writes its own slot of partRR.
+struct DdBiCgStab {
+    using State = BiState;
+    static_assert(sizeof(BiState) <= kSrStateBytes, "the read-back slot holds a BiState");
+    // half of DdCg's: an iteration is twice its launches and three exchanges
+    // instead of two, so four of them hide the host as eight of CG's do, and a
+    // converged solve leaves at most 2 * 4 - 1 iterations of ungated exchanges
+    static constexpr int kChunk = DdCg::kChunk / 2;
+    static DBuf<State> &control(Shard &s) { return s.bis; }
+    static size_t pair_len(gg_dd *d) { return (size_t)2 * d->P * d->G; }
+    static void ensure(gg_dd *d)
+    {
+        for (auto &sp : d->sh) {
+            Shard &s = *sp;
+            if (!s.bis.p) s.bis.alloc(1);
+            for (DBuf<double> *b : {&s.partR, &s.partRR}) {
+                if (b->p) continue;
+                b->alloc(pair_len(d));
+                GG_HIP(hipMemsetAsync(b->p, 0, pair_len(d) * sizeof(double), d->st));
+            }
+            for (DBuf<double> *b : {&s.bi_rt, &s.bi_t, &s.bi_q}) {
+                if (b->p) continue;
+                b->alloc(d->Pl);
+                GG_HIP(hipMemsetAsync(b->p, 0, d->Pl * sizeof(double), d->st));
+            }
+        }
+    }
+    static void zero(gg_dd *d)
+    {
+        for (auto &sp : d->sh) {
+            for (DBuf<double> *b : {&sp->partR, &sp->partRR})
+                GG_HIP(hipMemsetAsync(b->p, 0, pair_len(d) * sizeof(double), d->st));
+            for (DBuf<double> *b : {&sp->bi_rt, &sp->bi_t, &sp->bi_q})
+                GG_HIP(hipMemsetAsync(b->p, 0, d->Pl * sizeof(double), d->st));
+        }
+    }
+    static Gate gate(Shard &s, int k)
+    {
+        Gate g;
+        g.done = &s.bis.p->done;
+        g.mask = ~0;
+        g.nit = &s.bis.p->max_iter;
+        g.i = k;
+        return g;
+    }
+    static void enqueue_start(gg_dd *d)
+    {
+        const long long G2 = 2LL * d->G;
+        apply_minv(d, -1, 0, vec(&Shard::bv), vec(&Shard::bb));                    // bb = M b
+        dot(d, -1, 0, vec(&Shard::bb), vec(&Shard::bb), &Shard::partA);
+        for (auto &sp : d->sh) launch_normb(sp->partA.p, d->P * d->G, &sp->bis.p->normb, d->st);
+        spmv_rows(d, vec(&Shard::xv), vec(&Shard::bv), vec(&Shard::bi_q), true,
+                  [](Shard &) { return Gate{}; });                                  // q = b - A x
+        apply_minv(d, -1, 0, vec(&Shard::bi_q), vec(&Shard::rr));                  // r = M q
+        for (auto &sp : d->sh) {
+            Shard &s = *sp;
+            launch_dot(Gate{}, s.rr.p, s.rr.p, s.partRR.p + s.p * G2, d->G, dot_len(d, s), d->st);
+        }
+        exchange(d, vec(&Shard::partRR), 0, G2);
+        for (auto &sp : d->sh) {
+            Shard &s = *sp;
+            launch_bi_p_r(Gate{}, 0, true, s.bis.p, s.partRR.p, d->P, d->G, s.w.p, nullptr, s.rr.p, s.bi_rt.p,
+                          s.hist.p, d->H0, d->st);                                  // rt = p = r
+        }
+    }
+    static void enqueue_iterations(gg_dd *d, int k0, int k1)
+    {
+        const int NP = d->P * d->G;
+        const long long G2 = 2LL * d->G, H0 = d->H0;
+        for (int k = k0; k < k1; k++) {
+            const GateOf gt = [k](Shard &s) { return gate(s, k); };
+            int mk = prof_begin(d, GG_DD_PROF_SPMV, k);
+            spmv_rows(d, vec(&Shard::w), Get{}, vec(&Shard::bi_q), false, gt);      // q = A p
+            prof_end(d, mk);
+            apply_minv(d, gt, k, vec(&Shard::bi_q), vec(&Shard::ww));               // v = M q
+            mk = prof_begin(d, GG_DD_PROF_ORTH, k);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_cg_pq(gt(s), s.bi_rt.p, s.ww.p, s.partA.p + (long long)s.p * d->G, d->G, dot_len(d, s),
+                             d->st);
+            }
+            exchange(d, vec(&Shard::partA), 0, d->G);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_bi_s_r(gt(s), k, s.bis.p, s.partA.p, NP, s.rr.p, s.ww.p, d->G, H0, d->st);   // s in place of r
+            }
+            prof_end(d, mk);
+            mk = prof_begin(d, GG_DD_PROF_SPMV, k);
+            spmv_rows(d, vec(&Shard::rr), Get{}, vec(&Shard::bi_q), false, gt);     // q = A s
+            prof_end(d, mk);
+            apply_minv(d, gt, k, vec(&Shard::bi_q), vec(&Shard::bi_t));             // t = M q
+            mk = prof_begin(d, GG_DD_PROF_ORTH, k);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_cg_rz(gt(s), s.rr.p, s.bi_t.p, s.partR.p + s.p * G2, d->G, dot_len(d, s), d->st);   // s.t, t.t
+            }
+            exchange(d, vec(&Shard::partR), 0, G2);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_bi_xr_r(gt(s), s.bis.p, s.partR.p, d->P, d->G, s.xv.p, s.w.p, s.rr.p, s.bi_t.p, s.bi_rt.p,
+                               s.partRR.p + s.p * G2, H0, dot_len(d, s), d->st);
+            }
+            prof_end(d, mk);
+            mk = prof_begin(d, GG_DD_PROF_ORTH, k);
+            exchange(d, vec(&Shard::partRR), 0, G2);
+            for (auto &sp : d->sh) {
+                Shard &s = *sp;
+                launch_bi_p_r(gt(s), k, false, s.bis.p, s.partRR.p, d->P, d->G, s.w.p, s.ww.p, s.rr.p, nullptr,
+                              s.hist.p, H0, d->st);
+            }
+            prof_end(d, mk);
+        }
+    }
+    static std::string breakdown(const State &h)
+    {
+        const char *name = h.why == BI_WHY_RTV ? "rt.v" : h.why == BI_WHY_OMEGA ? "omega" : "rho";
+        char val[40];
+        std::snprintf(val, sizeof val, "%g", h.bad);
+        return "gg_dd_solve_bicgstab: BiCGStab broke down at iteration " + std::to_string(h.it) + ": " + name +
+               " = " + val + " (zero or not finite)";
+    }
+};
+
+// the method of a sharded solve or transient step: by opt->flags (gg_dd_solve,
+// gg_dd_transient*: GMRES(m) or GG_SOLVE_CG) or BiCGStab (the *_bicgstab entry points)
+enum class DdMethod { BY_FLAGS, BICGSTAB };
+
 // the options every sharded solve takes (gg_dd_solve, and a step of the transient loop)
 void check_options(gg_dd *d, const gg_options *opt, const std::string &who)
 {
@@ -1095,10 +1237,23 @@ void check_options(gg_dd *d, const gg_options *opt, const std::string &who)
     const int m = opt->restart;
     GG_REQUIRE(m >= 1 && m <= 512, GG_EINVAL, who + ": restart must be in [1, 512]");
     GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, who + ": negative max_iter");
-    // (GG_SOLVE_BICGSTAB is not offered on shards: an unknown flag here)
+    // (GG_SOLVE_BICGSTAB is an unknown flag here, as it always was: sharded
+    // BiCGStab comes through gg_dd_solve_bicgstab, check_options_bicgstab below)
     GG_REQUIRE((opt->flags & ~(GG_SOLVE_CGS2 | GG_SOLVE_CG)) == 0, GG_EINVAL, who + ": unknown flags");
     GG_REQUIRE(opt->flags != (GG_SOLVE_CGS2 | GG_SOLVE_CG), GG_EINVAL,
                who + ": GG_SOLVE_CG orthogonalizes nothing (GG_SOLVE_CGS2 does not apply)");
+}
+
+// the *_bicgstab entry points': flags 0 or GG_SOLVE_BICGSTAB, both BiCGStab;
+// restart validated and otherwise ignored, as for GG_SOLVE_CG above
+void check_options_bicgstab(gg_dd *d, const gg_options *opt, const std::string &who)
+{
+    GG_REQUIRE(d->have, GG_ESTATE, who + ": no system (call gg_dd_set_system)");
+    GG_REQUIRE(opt, GG_EINVAL, who + ": null options");
+    GG_REQUIRE(opt->restart >= 1 && opt->restart <= 512, GG_EINVAL, who + ": restart must be in [1, 512]");
+    GG_REQUIRE(opt->max_iter >= 0, GG_EINVAL, who + ": negative max_iter");
+    GG_REQUIRE(opt->flags == 0 || opt->flags == GG_SOLVE_BICGSTAB, GG_EINVAL,
+               who + ": flags must be 0 or GG_SOLVE_BICGSTAB");
 }
 
 // GMRES(m) in the same three parts as the short-recurrence solve above:
@@ -1198,8 +1353,13 @@ int gmres_finish(gg_dd *d, const GmresEnd &o, gg_result *res, bool want_hist = t
     return o.ret;
 }
 
-int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res, DdMethod method)
 {
+    if (method == DdMethod::BICGSTAB) {
+        check_options_bicgstab(d, opt, "gg_dd_solve_bicgstab");
+        set_dev(d);
+        return solve_short_recurrence<DdBiCgStab>(d, d_b, d_x, opt, res);
+    }
     check_options(d, opt, "gg_dd_solve");
     d->cgs2 = (opt->flags & GG_SOLVE_CGS2) != 0;
     set_dev(d);
@@ -1212,11 +1372,12 @@ int solve_once(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, 
     return gmres_finish(d, o, res);
 }
 
-int solve_dev(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+int solve_dev(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res,
+              DdMethod method = DdMethod::BY_FLAGS)
 {
     for (int attempt = 0;; attempt++) {
         try {
-            return solve_once(d, d_b, d_x, opt, res);
+            return solve_once(d, d_b, d_x, opt, res, method);
         } catch (Fallback &f) {
             if (attempt >= 2) throw Error{GG_EHIP, "gg_dd_solve: fallbacks exhausted"};
             apply_fallback(d, f);
@@ -1427,7 +1588,7 @@ void fetch_nat(gg_dd *d, const DBuf<double> &buf, double *h)
 // shards' slots (Shard::xv) from the one gather_in before step 1 to the one
 // scatter_out after the last step; a step enqueues the source values (one launch
 // per process), the right-hand side in slot order (one launch per shard, xv ->
-// bv), the solve's middle part (sr_run / gmres_run: no load, no store), and the
+// bv), the solve's middle part (sr_run of CG or BiCGStab / gmres_run: no load, no store), and the
 // port capture (one launch).  No natural-order vector is touched per step.
 //
 // Tables per call, built on the host from the slot -> row maps.  INVARIANT: every
@@ -1442,10 +1603,13 @@ struct TransientShard {
 
 int transient_dd(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
                  const std::vector<int> &kind, const std::vector<int> &dptr, const std::vector<double> &data,
-                 int nport, const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total)
+                 int nport, const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total,
+                 DdMethod method = DdMethod::BY_FLAGS)
 {
     // every check before anything is enqueued: every rank refuses alike
-    check_options(d, opt, "gg_dd_transient");
+    const bool bi = method == DdMethod::BICGSTAB;
+    if (bi) check_options_bicgstab(d, opt, "gg_dd_transient_bicgstab");
+    else check_options(d, opt, "gg_dd_transient");
     GG_REQUIRE(nport == 0 || (port && port_out), GG_EINVAL, "gg_dd_transient: null port arrays");
     const int n = d->n;
     for (int k = 0; k < nsrc; k++)
@@ -1453,8 +1617,8 @@ int transient_dd(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, 
     for (int j = 0; j < nport; j++)
         GG_REQUIRE(port[j] >= 0 && port[j] < n, GG_EINVAL, "gg_dd_transient: port out of range");
     set_dev(d);
-    d->cgs2 = (opt->flags & GG_SOLVE_CGS2) != 0;
-    const bool cg = (opt->flags & GG_SOLVE_CG) != 0;
+    d->cgs2 = !bi && (opt->flags & GG_SOLVE_CGS2) != 0;
+    const bool cg = !bi && (opt->flags & GG_SOLVE_CG) != 0;
     const long long H0 = d->H0;
     // B^T by natural row: the sources of each row in ascending k
     std::vector<int> nptr(n + 1, 0), nidx(nsrc);
@@ -1518,7 +1682,8 @@ int transient_dd(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, 
         total = 0;
         status = GG_OK;
         GG_HIP(hipMemsetAsync(d_pv.p, 0, npv * sizeof(double), d->st));
-        if (cg) sr_prepare<DdCg>(d, opt);
+        if (bi) sr_prepare<DdBiCgStab>(d, opt);
+        else if (cg) sr_prepare<DdCg>(d, opt);
         else gmres_prepare(d, opt);
         gather_in(d, d->nat_b.p, &Shard::xv);
         ShardPtrs xs{};
@@ -1534,7 +1699,10 @@ int transient_dd(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, 
             gg_result r{};
             int rc;
             const bool last = it == nsteps;                 // gg_dd_get_history: the last step's
-            if (cg) {
+            if (bi) {
+                const BiState e = sr_run<DdBiCgStab>(d, opt, hint > 0 ? hint + 2 : DdBiCgStab::kChunk);
+                rc = sr_finish<DdBiCgStab>(d, e, &r, true, last);
+            } else if (cg) {
                 const CgState e = sr_run<DdCg>(d, opt, hint > 0 ? hint + 2 : DdCg::kChunk);
                 rc = sr_finish<DdCg>(d, e, &r, true, last);
             } else {
@@ -1883,9 +2051,33 @@ int gg_dd_solve(gg_dd *d, const double *b, double *x, const gg_options *opt, gg_
     GG_API_END
 }
 
-int gg_dd_transient_src(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
-                        const int *src_kind, const int *src_ptr, const double *src_data, int nport,
-                        const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total)
+int gg_dd_solve_bicgstab_device(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt, gg_result *res)
+{
+    GG_API_BEGIN
+    GG_REQUIRE(d && d_b && d_x, GG_EINVAL, "null argument");
+    return solve_dev(d, d_b, d_x, opt, res, DdMethod::BICGSTAB);
+    GG_API_END
+}
+
+int gg_dd_solve_bicgstab(gg_dd *d, const double *b, double *x, const gg_options *opt, gg_result *res)
+{
+    GG_API_BEGIN
+    GG_REQUIRE(d && b && x, GG_EINVAL, "null argument");
+    GG_REQUIRE(d->have, GG_ESTATE, "gg_dd_solve_bicgstab: no system");
+    set_dev(d);
+    stage_nat(d, d->nat_a, b);
+    stage_nat(d, d->nat_b, x);
+    int rc = solve_dev(d, d->nat_a.p, d->nat_b.p, opt, res, DdMethod::BICGSTAB);
+    if (rc >= 0 || rc == GG_EBREAKDOWN) fetch_nat(d, d->nat_b, x);       // (a breakdown: the last iterate)
+    return rc;
+    GG_API_END
+}
+
+// gg_dd_transient_src and gg_dd_transient_bicgstab_src
+static int transient_src_entry(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                               const int *src_kind, const int *src_ptr, const double *src_data, int nport,
+                               const int *port, double *x, const gg_options *opt, double *port_out,
+                               int *iters_total, DdMethod method)
 {
     GG_API_BEGIN
     GG_REQUIRE(d && opt && x && cdiag && iters_total, GG_EINVAL, "null argument");
@@ -1895,13 +2087,14 @@ int gg_dd_transient_src(gg_dd *d, int nsteps, double h, const double *cdiag, int
     std::vector<double> data;
     source_tables(nsrc, src_kind, src_ptr, src_data, kind, dptr, data);
     return transient_dd(d, nsteps, h, cdiag, nsrc, src_node, kind, dptr, data, nport, port, x, opt, port_out,
-                        iters_total);
+                        iters_total, method);
     GG_API_END
 }
 
-int gg_dd_transient(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
-                    const double *pulse, int nport, const int *port, double *x, const gg_options *opt,
-                    double *port_out, int *iters_total)
+// gg_dd_transient and gg_dd_transient_bicgstab
+static int transient_pulse_entry(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
+                                 const int *src_node, const double *pulse, int nport, const int *port, double *x,
+                                 const gg_options *opt, double *port_out, int *iters_total, DdMethod method)
 {
     GG_API_BEGIN
     GG_REQUIRE(d && opt && x && cdiag && iters_total, GG_EINVAL, "null argument");
@@ -1911,8 +2104,41 @@ int gg_dd_transient(gg_dd *d, int nsteps, double h, const double *cdiag, int nsr
     for (int k = 0; k <= nsrc; k++) dptr[k] = 7 * k;
     std::vector<double> data(pulse, pulse + (size_t)7 * nsrc);
     return transient_dd(d, nsteps, h, cdiag, nsrc, src_node, kind, dptr, data, nport, port, x, opt, port_out,
-                        iters_total);
+                        iters_total, method);
     GG_API_END
+}
+
+int gg_dd_transient_src(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                        const int *src_kind, const int *src_ptr, const double *src_data, int nport,
+                        const int *port, double *x, const gg_options *opt, double *port_out, int *iters_total)
+{
+    return transient_src_entry(d, nsteps, h, cdiag, nsrc, src_node, src_kind, src_ptr, src_data, nport, port, x,
+                               opt, port_out, iters_total, DdMethod::BY_FLAGS);
+}
+
+int gg_dd_transient(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                    const double *pulse, int nport, const int *port, double *x, const gg_options *opt,
+                    double *port_out, int *iters_total)
+{
+    return transient_pulse_entry(d, nsteps, h, cdiag, nsrc, src_node, pulse, nport, port, x, opt, port_out,
+                                 iters_total, DdMethod::BY_FLAGS);
+}
+
+int gg_dd_transient_bicgstab_src(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
+                                 const int *src_node, const int *src_kind, const int *src_ptr,
+                                 const double *src_data, int nport, const int *port, double *x,
+                                 const gg_options *opt, double *port_out, int *iters_total)
+{
+    return transient_src_entry(d, nsteps, h, cdiag, nsrc, src_node, src_kind, src_ptr, src_data, nport, port, x,
+                               opt, port_out, iters_total, DdMethod::BICGSTAB);
+}
+
+int gg_dd_transient_bicgstab(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc, const int *src_node,
+                             const double *pulse, int nport, const int *port, double *x, const gg_options *opt,
+                             double *port_out, int *iters_total)
+{
+    return transient_pulse_entry(d, nsteps, h, cdiag, nsrc, src_node, pulse, nport, port, x, opt, port_out,
+                                 iters_total, DdMethod::BICGSTAB);
 }
 
 int gg_dd_set_transient_hint(gg_dd *d, int on)

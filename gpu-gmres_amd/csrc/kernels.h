@@ -436,6 +436,20 @@ void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, 
 //   SR_INIT, rho = rr zero or not finite: SR_BREAKDOWN, else rt = p = r
 void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
                  const double *r, double *rt, double *hist, long long Ppad, hipStream_t st, Batch bt = {});
+// The sharded solve (dd.hip), as CG's above: launch_cg_pq and launch_cg_rz with Ppad = the dot range
+// and part = the shard's slot of an all-gathered array, and these three over every shard's partials:
+//   launch_bi_s with part = nparts_in = P * G contiguous partials (grid G, Ppad = H0)
+void launch_bi_s_r(Gate g, int it, BiState *bs, const double *part, int nparts_in, double *r, const double *v,
+                   int G, long long Ppad, hipStream_t st);
+//   launch_bi_xr with part_in = P slots of 2 G doubles (t . s's G, then t . t's); x and r updated over
+//   Ppad = H0, the partials of r . r and rt . r taken over [0, dot_len) alone (k_cg_rz's bits there)
+//   into part_out_slot = this shard's 2 G slot of a second gathered array, distinct from part_in's
+void launch_bi_xr_r(Gate g, BiState *bs, const double *part_in, int P, int G, double *x, const double *p,
+                    double *s, const double *t, const double *rt, double *part_out_slot, long long Ppad,
+                    long long dot_len, hipStream_t st);
+//   launch_bi_p with part = P slots of 2 G doubles (r . r's G, then rt . r's; start: r . r's alone)
+void launch_bi_p_r(Gate g, int it, bool start, BiState *bs, const double *part, int P, int G, double *p,
+                   const double *v, const double *r, double *rt, double *hist, long long Ppad, hipStream_t st);
 
 // ---- batched (many-RHS) launches with kernels or loops of their own (the rest
 // of the batch runs the launchers above with a Batch): nsc scenarios per launch,

@@ -252,6 +252,13 @@ __global__ __launch_bounds__(kBlock) void k_cg_p(Gate g, int it, CgState *cs, co
 // by thread 0 of block 0 alone.  alpha and omega are stored by one launch and
 // read by later ones only; rho alternates between two words like CG's rz.
 // zs: the many-RHS batch (bicgstab_batch.hip), as the CG kernels above.
+//
+// The sharded solve (dd.hip "Sharded BiCGStab") runs them as it runs CG's: grid
+// G per shard, the updates over the shard's H0 slots, a dot over its dot range
+// alone, its partials in the shard's slot of an all-gathered array.  k_bi_s
+// takes rt.v's slots, G doubles each and so contiguous, as G = P * G;
+// k_bi_xr<true> and k_bi_p<START, true> take the paired dots' slots, 2 G
+// doubles each, through sum_partials_sh.
 __device__ __forceinline__ bool bi_bad(double v) { return !isfinite(v) || v == 0.0; }
 
 // rtv from the partials (breakdown when zero or not finite: nothing moves);
@@ -312,11 +319,19 @@ __global__ __launch_bounds__(kBlock) void k_bi_s(Gate g, int it, BiState *bs, co
 // x = omega s + (alpha p + x);  r = (-omega) t + s in place of s; the block
 // partials of r . r (part_out[b]) and rt . r (part_out[G + b]) from the r values
 // in registers, each thread's units ascending (k_dot's order)
+// SH: the sharded solve -- part_in holds P slots of 2 G doubles (t.s's G, then
+// t.t's); the updates run over units (H0 / 2) and the partials over the units
+// below dunits (the shard's dot range / 2) alone, so they are bit for bit what
+// k_cg_rz gives over the dot range with grid G; part_out is the shard's own 2 G
+// slot of a SECOND gathered array -- every block reads all of part_in's array
+// while other blocks (and other shards) write part_out's
+template <bool SH = false>
 __global__ __launch_bounds__(kBlock) void k_bi_xr(Gate g, BiState *bs, const double *part_in, int G,
                                                   double *__restrict__ x, const double *__restrict__ p,
                                                   double *__restrict__ s, const double *__restrict__ t,
                                                   const double *__restrict__ rt, double *part_out,
-                                                  long long units, long long zs = 0)
+                                                  long long units, long long zs = 0, int P = 1,
+                                                  long long dunits = 0)
 {
     if (gated_z(g, zs, blockIdx.y)) return;
     bs = zp(bs, zs, blockIdx.y);
@@ -344,8 +359,8 @@ __global__ __launch_bounds__(kBlock) void k_bi_xr(Gate g, BiState *bs, const dou
         }
     };
     load();
-    const double ts = sum_partials(part_in, G);
-    const double tt = sum_partials(part_in + G, G);
+    const double ts = SH ? sum_partials_sh(part_in, P, G, 2LL * G) : sum_partials(part_in, G);
+    const double tt = SH ? sum_partials_sh(part_in + G, P, G, 2LL * G) : sum_partials(part_in + G, G);
     const double omega = tt > 0.0 ? ts / tt : 0.0;
     const double alpha = bs->alpha;
     if (blockIdx.x == 0 && threadIdx.x == 0) bs->omega = omega;
@@ -362,10 +377,12 @@ __global__ __launch_bounds__(kBlock) void k_bi_xr(Gate g, BiState *bs, const dou
                 sv[j].y = no * tv[j].y + sv[j].y;
                 st2(x, u, xv[j]);
                 st2(s, u, sv[j]);
-                acc[0] += sv[j].x * sv[j].x;
-                acc[0] += sv[j].y * sv[j].y;
-                acc[1] += qv[j].x * sv[j].x;
-                acc[1] += qv[j].y * sv[j].y;
+                if (!SH || u < dunits) {
+                    acc[0] += sv[j].x * sv[j].x;
+                    acc[0] += sv[j].y * sv[j].y;
+                    acc[1] += qv[j].x * sv[j].x;
+                    acc[1] += qv[j].y * sv[j].y;
+                }
             }
         }
         u0 += kUnroll * stride;
@@ -380,11 +397,12 @@ __global__ __launch_bounds__(kBlock) void k_bi_xr(Gate g, BiState *bs, const dou
 // p = beta ((-omega) v + p) + r with beta = (rhon / rho) (alpha / omega)
 // (START: rt = p = r).  it: the iteration's 0-based index (START: the initial
 // residual, nothing counted)
-template <bool START>
+// SH: the sharded solve -- part holds P slots of 2 G doubles (r.r's G, then rt.r's)
+template <bool START, bool SH = false>
 __global__ __launch_bounds__(kBlock) void k_bi_p(Gate g, int it, BiState *bs, const double *part, int G,
                                                  double *__restrict__ p, const double *__restrict__ v,
                                                  const double *__restrict__ r, double *__restrict__ rt,
-                                                 double *hist, long long units, long long zs = 0)
+                                                 double *hist, long long units, long long zs = 0, int P = 1)
 {
     if (gated_z(g, zs, blockIdx.y)) return;
     bs = zp(bs, zs, blockIdx.y);
@@ -411,8 +429,8 @@ __global__ __launch_bounds__(kBlock) void k_bi_p(Gate g, int it, BiState *bs, co
         }
     };
     load();
-    const double rr = sum_partials(part, G);
-    const double rhon = START ? rr : sum_partials(part + G, G);
+    const double rr = SH ? sum_partials_sh(part, P, G, 2LL * G) : sum_partials(part, G);
+    const double rhon = START ? rr : SH ? sum_partials_sh(part + G, P, G, 2LL * G) : sum_partials(part + G, G);
     const double res = sqrt(rr) / bs->normb;
     const double omega = START ? 1.0 : bs->omega;
     const double alpha = START ? 1.0 : bs->alpha;
@@ -537,7 +555,7 @@ void launch_bi_s(Gate g, int it, BiState *bs, const double *part, int G, double 
 void launch_bi_xr(Gate g, BiState *bs, const double *part_in, int G, double *x, const double *p, double *s,
                   const double *t, const double *rt, double *part_out, long long Ppad, hipStream_t st, Batch bt)
 {
-    k_bi_xr<<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, bs, part_in, G, x, p, s, t, rt, part_out, Ppad / 2, bt.zs);
+    k_bi_xr<false><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, bs, part_in, G, x, p, s, t, rt, part_out, Ppad / 2, bt.zs);
 }
 void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, int G, double *p, const double *v,
                  const double *r, double *rt, double *hist, long long Ppad, hipStream_t st, Batch bt)
@@ -546,6 +564,27 @@ void launch_bi_p(Gate g, int it, bool start, BiState *bs, const double *part, in
         k_bi_p<true><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2, bt.zs);
     else
         k_bi_p<false><<<dim3(G, bt.nsc), kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2, bt.zs);
+}
+// the sharded solve's consumers (dd.hip): nparts_in = P * G contiguous partials; P slots of 2 G
+void launch_bi_s_r(Gate g, int it, BiState *bs, const double *part, int nparts_in, double *r, const double *v,
+                   int G, long long Ppad, hipStream_t st)
+{
+    k_bi_s<<<G, kBlock, 0, st>>>(g, it, bs, part, nparts_in, r, v, Ppad / 2, 0);
+}
+void launch_bi_xr_r(Gate g, BiState *bs, const double *part_in, int P, int G, double *x, const double *p,
+                    double *s, const double *t, const double *rt, double *part_out_slot, long long Ppad,
+                    long long dot_len, hipStream_t st)
+{
+    k_bi_xr<true><<<G, kBlock, 0, st>>>(g, bs, part_in, G, x, p, s, t, rt, part_out_slot, Ppad / 2, 0, P,
+                                        dot_len / 2);
+}
+void launch_bi_p_r(Gate g, int it, bool start, BiState *bs, const double *part, int P, int G, double *p,
+                   const double *v, const double *r, double *rt, double *hist, long long Ppad, hipStream_t st)
+{
+    if (start)
+        k_bi_p<true, true><<<G, kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2, 0, P);
+    else
+        k_bi_p<false, true><<<G, kBlock, 0, st>>>(g, it, bs, part, G, p, v, r, rt, hist, Ppad / 2, 0, P);
 }
 
 }  // namespace gg

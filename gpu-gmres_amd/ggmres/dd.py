@@ -1,5 +1,5 @@
-"""Sharded GMRES(m) or conjugate gradients + ILU(0) over P GPUs (include/ggmres_dd.h,
-SURVEY.md 8(e)).
+"""Sharded GMRES(m), conjugate gradients or BiCGStab + ILU(0) over P GPUs
+(include/ggmres_dd.h).
 
 DD(nparts, device=0)                    all shards in this process on one GPU
 DD(nparts, rank=r, uid=bytes, device=d) one shard per process (RCCL); uid from
@@ -33,7 +33,9 @@ EXPORTS = ["gg_dd_unique_id", "gg_dd_create", "gg_dd_destroy", "gg_dd_comm_ranks
            "gg_dd_perm", "gg_dd_dot_layout", "gg_dd_solve", "gg_dd_solve_device",
            "gg_dd_transient_src", "gg_dd_transient", "gg_dd_set_transient_hint", "gg_dd_get_history", "gg_dd_spmv", "gg_dd_precond_apply", "gg_dd_set_division",
            "gg_dd_time_exchange", "gg_dd_profile_enable", "gg_dd_profile_reset", "gg_dd_profile_get",
-           "gg_dd_bytes"]
+           "gg_dd_bytes",
+           "gg_dd_solve_bicgstab", "gg_dd_solve_bicgstab_device",
+           "gg_dd_transient_bicgstab_src", "gg_dd_transient_bicgstab"]
 # gg_dd_prof_kind (ggmres_dd.h)
 PROF_SPMV, PROF_TRSV_L, PROF_SEP, PROF_TRSV_U, PROF_ORTH = range(5)
 PROF_NAMES = ("spmv", "trsv_L", "separator", "trsv_U", "orthogonalization")
@@ -65,6 +67,10 @@ def _lib():
         L.gg_dd_transient.argtypes = [_VP, ctypes.c_int, ctypes.c_double, _D, ctypes.c_int, _I, _D,
                                       ctypes.c_int, _VP, _D, ctypes.POINTER(Options), _VP,
                                       ctypes.POINTER(ctypes.c_int)]
+        L.gg_dd_solve_bicgstab.argtypes = L.gg_dd_solve.argtypes
+        L.gg_dd_solve_bicgstab_device.argtypes = L.gg_dd_solve_device.argtypes
+        L.gg_dd_transient_bicgstab_src.argtypes = L.gg_dd_transient_src.argtypes
+        L.gg_dd_transient_bicgstab.argtypes = L.gg_dd_transient.argtypes
         L.gg_dd_set_transient_hint.argtypes = [_VP, ctypes.c_int]
         L.gg_dd_get_history.argtypes = [_VP, _VP, ctypes.c_int]
         L.gg_dd_spmv.argtypes = [_VP, _D, _D]
@@ -165,21 +171,36 @@ class DD:
         ggmres.SOLVE_CG for conjugate gradients (B and its ILU(0) SPD): ret is then
         0, 1 or ggmres.EBREAKDOWN -- returned, not raised, with x the last iterate,
         the history and the counts, as ggmres.Solver.solve does"""
+        return self._solve(_lib().gg_dd_solve, b, x0, restart, max_iter, tol, flags)
+
+    def _solve(self, fn, b, x0, restart, max_iter, tol, flags):
         b = np.ascontiguousarray(b, np.float64)
         x = np.zeros(self.n) if x0 is None else np.array(x0, np.float64, copy=True)
         o = Options(int(restart), int(max_iter), float(tol), int(flags))
         r = Result()
-        rc = _check(_lib().gg_dd_solve(self.h, b, x, ctypes.byref(o), ctypes.byref(r)), allow_nc=True)
+        rc = _check(fn(self.h, b, x, ctypes.byref(o), ctypes.byref(r)), allow_nc=True)
         return dict(ret=rc, x=x, iters=r.iters, inner=r.inner_iters, restarts=r.restarts,
                     relres=r.relres, solve_ms=r.solve_ms, hist=self.history())
 
     def solve_device(self, b_ptr, x_ptr, restart=30, max_iter=3000, tol=1e-10, flags=0):
+        return self._solve_device(_lib().gg_dd_solve_device, b_ptr, x_ptr, restart, max_iter, tol, flags)
+
+    def _solve_device(self, fn, b_ptr, x_ptr, restart, max_iter, tol, flags):
         o = Options(int(restart), int(max_iter), float(tol), int(flags))
         r = Result()
-        rc = _check(_lib().gg_dd_solve_device(self.h, _VP(b_ptr), _VP(x_ptr), ctypes.byref(o),
-                                              ctypes.byref(r)), allow_nc=True)
+        rc = _check(fn(self.h, _VP(b_ptr), _VP(x_ptr), ctypes.byref(o), ctypes.byref(r)), allow_nc=True)
         return dict(ret=rc, iters=r.iters, inner=r.inner_iters, restarts=r.restarts,
                     relres=r.relres, solve_ms=r.solve_ms)
+
+    def solve_bicgstab(self, b, x0=None, restart=30, max_iter=3000, tol=1e-10, flags=0):
+        """gg_dd_solve_bicgstab: BiCGStab on the shards (flags 0 or ggmres.SOLVE_BICGSTAB,
+        both BiCGStab -- DD.solve refuses that flag); the dict of solve, ret 0, 1 or
+        ggmres.EBREAKDOWN (returned, not raised, with x the last iterate)"""
+        return self._solve(_lib().gg_dd_solve_bicgstab, b, x0, restart, max_iter, tol, flags)
+
+    def solve_bicgstab_device(self, b_ptr, x_ptr, restart=30, max_iter=3000, tol=1e-10, flags=0):
+        return self._solve_device(_lib().gg_dd_solve_bicgstab_device, b_ptr, x_ptr, restart, max_iter, tol,
+                                  flags)
 
     def _transient_io(self, nsteps, ports, x0, x_fill, port_fill):
         """the in/out state, the port array (preset to port_fill) and the rows of x
@@ -213,6 +234,18 @@ class DD:
         rows of x this process does not hold (e.g. NaN), so a rank sees what it wrote.
         Environment GG_DD_TRANSIENT_HINT=0, read at every call (set it alike on every
         rank): the CG steps take no hint (gg_dd_set_transient_hint)."""
+        return self._transient_src(_lib().gg_dd_transient_src, nsteps, h, cdiag, src_node, sources, ports, x0,
+                                   restart, max_iter, tol, flags, x_fill, port_fill)
+
+    def transient_bicgstab_src(self, nsteps, h, cdiag, src_node, sources, ports, x0, restart=32, max_iter=10000,
+                               tol=1e-7, flags=0, x_fill=None, port_fill=None):
+        """gg_dd_transient_bicgstab_src: transient_src with every step a BiCGStab solve
+        (flags 0 or ggmres.SOLVE_BICGSTAB); the steps take the hint as CG's do"""
+        return self._transient_src(_lib().gg_dd_transient_bicgstab_src, nsteps, h, cdiag, src_node, sources,
+                                   ports, x0, restart, max_iter, tol, flags, x_fill, port_fill)
+
+    def _transient_src(self, fn, nsteps, h, cdiag, src_node, sources, ports, x0, restart, max_iter, tol, flags,
+                       x_fill, port_fill):
         x, ports, pv, own = self._transient_io(nsteps, ports, x0, x_fill, port_fill)
         src_node = np.ascontiguousarray(src_node, np.int32)
         kind = np.array([k for k, _ in sources], np.int32)
@@ -222,7 +255,7 @@ class DD:
         tot = ctypes.c_int()
         o = Options(int(restart), int(max_iter), float(tol), int(flags))
         one = np.zeros(1, np.int32)
-        rc = _check(_lib().gg_dd_transient_src(
+        rc = _check(fn(
             self.h, int(nsteps), float(h), np.ascontiguousarray(cdiag, np.float64), len(src_node),
             src_node if len(src_node) else one, kind if len(kind) else one, ptr, data, len(ports),
             ports.ctypes.data if len(ports) else None, x, ctypes.byref(o),
@@ -232,12 +265,23 @@ class DD:
     def transient(self, nsteps, h, cdiag, src_node, pulse, ports, x0, restart=32, max_iter=10000,
                   tol=1e-7, flags=0, x_fill=None, port_fill=None):
         """gg_dd_transient: transient_src with PULSE rows pulse[nsrc, 7]"""
+        return self._transient(_lib().gg_dd_transient, nsteps, h, cdiag, src_node, pulse, ports, x0, restart,
+                               max_iter, tol, flags, x_fill, port_fill)
+
+    def transient_bicgstab(self, nsteps, h, cdiag, src_node, pulse, ports, x0, restart=32, max_iter=10000,
+                           tol=1e-7, flags=0, x_fill=None, port_fill=None):
+        """gg_dd_transient_bicgstab: transient_bicgstab_src with PULSE rows pulse[nsrc, 7]"""
+        return self._transient(_lib().gg_dd_transient_bicgstab, nsteps, h, cdiag, src_node, pulse, ports, x0,
+                               restart, max_iter, tol, flags, x_fill, port_fill)
+
+    def _transient(self, fn, nsteps, h, cdiag, src_node, pulse, ports, x0, restart, max_iter, tol, flags,
+                   x_fill, port_fill):
         x, ports, pv, own = self._transient_io(nsteps, ports, x0, x_fill, port_fill)
         src_node = np.ascontiguousarray(src_node, np.int32)
         pulse = np.ascontiguousarray(pulse, np.float64).reshape(-1)
         tot = ctypes.c_int()
         o = Options(int(restart), int(max_iter), float(tol), int(flags))
-        rc = _check(_lib().gg_dd_transient(
+        rc = _check(fn(
             self.h, int(nsteps), float(h), np.ascontiguousarray(cdiag, np.float64), len(src_node),
             src_node if len(src_node) else np.zeros(1, np.int32), pulse if pulse.size else np.zeros(7),
             len(ports), ports.ctypes.data if len(ports) else None, x, ctypes.byref(o),

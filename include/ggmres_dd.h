@@ -1,6 +1,7 @@
 /*
  * ggmres_dd.h -- C ABI of the sharded (domain-decomposed) solve, SURVEY.md 8(e):
- * GMRES(m), or conjugate gradients (GG_SOLVE_CG, below).
+ * GMRES(m), conjugate gradients (GG_SOLVE_CG, below), or BiCGStab through entry
+ * points of its own (gg_dd_solve_bicgstab, below).
  *
  * Replaces the reference's multi-domain path: partition4 (src/partition3.cpp:122-194,
  * METIS_PartGraphRecursive -> our recursive BFS bisection / contiguous blocks),
@@ -40,7 +41,11 @@
  *                  it has read: one host wait per chunk, none per iteration.
  *   Any other combination is GG_EINVAL: GG_SOLVE_CG with GG_SOLVE_CGS2 (CG
  *   orthogonalizes nothing), and GG_SOLVE_BICGSTAB, which the sharded solve
- *   does not offer.
+ *   does not offer through these entry points: gg_dd_solve, gg_dd_solve_device,
+ *   gg_dd_transient_src and gg_dd_transient answer it with GG_EINVAL, as they
+ *   always have -- callers and tests rely on that refusal -- so sharded BiCGStab
+ *   has a door of its own, gg_dd_solve_bicgstab and its kin below, named as the
+ *   batches are (gg_solve_bicgstab_batch, gg_transient_bicgstab_batch).
  *
  * Three communicators:
  *   GG_DD_RCCL   one process per GPU (torchrun), shard = rank, RCCL collectives
@@ -136,6 +141,30 @@ int gg_dd_solve_device(gg_dd *d, const double *d_b, double *d_x, const gg_option
                        gg_result *res);
 int gg_dd_get_history(gg_dd *d, double *out, int cap);
 
+/* Sharded BiCGStab: ggmres.h's GG_SOLVE_BICGSTAB exactly (left-preconditioned,
+ * the recurrence of its description) on B with M = the sharded ILU(0) apply,
+ * for the nonsymmetric systems GG_SOLVE_CG does not serve; every communicator
+ * (GG_DD_LOOPBACK: timing only).  Why a second door: gg_dd_solve keeps answering
+ * GG_SOLVE_BICGSTAB with GG_EINVAL (above), so the method is reached here alone.
+ *   opt->flags: 0 or GG_SOLVE_BICGSTAB, both meaning BiCGStab; anything else is
+ *   GG_EINVAL.  restart is validated in [1, 512] and otherwise ignored, max_iter
+ *   >= 0, tol as there.  GG_ESTATE before gg_dd_set_system.
+ *   An iteration is two SpMVs, two applies and three all-gathers of dot partials
+ *   whatever its number: rt.v's G per shard, ONE of 2 G carrying t.s and t.t, ONE
+ *   of 2 G carrying r.r and rt.r.  No basis, no Hessenberg.
+ *   gg_result: iters = inner_iters = the iterations performed, restarts = 0,
+ *   relres = the last ||r|| / normb; gg_dd_get_history: the initial value, then
+ *   one entry per iteration.  GG_EBREAKDOWN when rt.v, omega or the next rho is
+ *   zero or not finite while the solve has not converged: x then holds the last
+ *   iterate on the rows this process holds, gg_last_error the text ("gg_dd_solve_
+ *   bicgstab: BiCGStab broke down at iteration k: <scalar> = <value> ..."), and
+ *   the object is clean for the next solve of any method.  The host enqueues the
+ *   iterations in chunks as for GG_SOLVE_CG (half as long); the results do not
+ *   depend on the chunk length. */
+int gg_dd_solve_bicgstab(gg_dd *d, const double *b, double *x, const gg_options *opt, gg_result *res);
+int gg_dd_solve_bicgstab_device(gg_dd *d, const double *d_b, double *d_x, const gg_options *opt,
+                                gg_result *res);
+
 /* The sharded backward-Euler transient loop: gg_transient_src of ggmres.h on the
  * system given to gg_dd_set_system (A = G + C/h; cdiag = C/h), over every
  * communicator (GG_DD_LOOPBACK: timing only, as for the solve).  Step it =
@@ -183,8 +212,19 @@ int gg_dd_transient_src(gg_dd *d, int nsteps, double h, const double *cdiag, int
 int gg_dd_transient(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
                     const int *src_node, const double *pulse, int nport, const int *port,
                     double *x, const gg_options *opt, double *port_out, int *iters_total);
-/* on = 0: the CG steps of the following gg_dd_transient* calls take no hint
- * (default 1); set it alike on every rank */
+/* The same two loops with every step a gg_dd_solve_bicgstab solve: arguments,
+ * outputs, checks and return value as above, opt->flags 0 or GG_SOLVE_BICGSTAB
+ * (anything else GG_EINVAL).  A step's first chunk takes the hint as a CG step's
+ * does; after a breakdown x keeps the step's last iterate and the loop goes on. */
+int gg_dd_transient_bicgstab_src(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
+                                 const int *src_node, const int *src_kind, const int *src_ptr,
+                                 const double *src_data, int nport, const int *port, double *x,
+                                 const gg_options *opt, double *port_out, int *iters_total);
+int gg_dd_transient_bicgstab(gg_dd *d, int nsteps, double h, const double *cdiag, int nsrc,
+                             const int *src_node, const double *pulse, int nport, const int *port,
+                             double *x, const gg_options *opt, double *port_out, int *iters_total);
+/* on = 0: the CG and BiCGStab steps of the following gg_dd_transient* calls take
+ * no hint (default 1); set it alike on every rank */
 int gg_dd_set_transient_hint(gg_dd *d, int on);
 
 /* single operators (host vectors, natural order) for parity tests */
@@ -207,7 +247,11 @@ int gg_dd_time_exchange(gg_dd *d, long long cnt, int reps, double *avg_us);
  * way: SPMV, TRSV_L, SEP and TRSV_U once per iteration, and under
  * GG_DD_PROF_ORTH -- CG orthogonalizes nothing -- its four launches with their
  * two all-gathers, as two marks per iteration: p.q partials | all-gather | x, r
- * update, and r.z, z.z partials | all-gather | p update.
+ * update, and r.z, z.z partials | all-gather | p update.  A gg_dd_solve_bicgstab
+ * solve: SPMV, TRSV_L, SEP and TRSV_U twice per iteration, and under
+ * GG_DD_PROF_ORTH three marks, one per all-gather with the launches around it:
+ * rt.v partials | all-gather | s; t.s, t.t partials | all-gather | x, r update;
+ * all-gather | p update.
  * kinds: a mask of (1 << GG_DD_PROF_*). */
 enum gg_dd_prof_kind {
     GG_DD_PROF_SPMV = 0, GG_DD_PROF_TRSV_L = 1, GG_DD_PROF_SEP = 2, GG_DD_PROF_TRSV_U = 3,

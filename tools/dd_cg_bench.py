@@ -27,6 +27,16 @@ GPU holds every shard -- GG_DD_LOCAL at P = the largest of --parts, CG and
 GMRES(30)/CGS2 to --tol, beside the single solver's CG on the same grid in the
 natural order; the arrow order's ILU(0) is another preconditioner, so the
 count differs.
+
+--bicgstab [--upwind U]: the same measurement with sharded BiCGStab
+(gg_dd_solve_bicgstab) in CG's place, on the grid made nonsymmetric
+(M.laplacian_5pt(grid, upwind=U), default 0.2) -- BiCGStab against GMRES(30)
+with MGS and with CGS2.  A BiCGStab iteration is two SpMVs, two applies and
+three all-gathers of dot partials; "orthogonalization" is its five launches with
+those (three marks per iteration).  --count-grid then reports BiCGStab's and
+GMRES(30)/CGS2's real iteration counts and solve times at P = the largest of
+--parts in one process (GG_DD_LOCAL, --reps solves each, interleaved, the median),
+and the single solver's BiCGStab count in the natural order.
 """
 import argparse
 import json
@@ -42,6 +52,12 @@ from ggmres.dd import DD, PROF_NAMES    # noqa: E402
 
 DIV = {"exact": ggmres.DIV_EXACT, "rcp": ggmres.DIV_RCP, "fma": ggmres.DIV_FMA}
 METHODS = (("cg", ggmres.SOLVE_CG), ("mgs", 0), ("cgs2", ggmres.SOLVE_CGS2))
+METHODS_BI = (("bicgstab", ggmres.SOLVE_BICGSTAB), ("mgs", 0), ("cgs2", ggmres.SOLVE_CGS2))
+
+
+def solve(d, name, b, **kw):
+    """DD.solve, or DD.solve_bicgstab for the method that has a door of its own"""
+    return (d.solve_bicgstab if name == "bicgstab" else d.solve)(b, **kw)
 
 
 def emit(**kw):
@@ -59,56 +75,92 @@ def main():
     p.add_argument("--division", choices=sorted(DIV), default="fma")
     p.add_argument("--count-grid", type=int, default=0)
     p.add_argument("--tol", type=float, default=1e-8)
+    p.add_argument("--bicgstab", action="store_true")
+    p.add_argument("--upwind", type=float, default=0.2)
     a = p.parse_args()
 
+    methods = METHODS_BI if a.bicgstab else METHODS
+    upwind = a.upwind if a.bicgstab else 0.0
     method = host.PART_GRID | host.PART_COLOR_SEP
-    A = M.laplacian_5pt(a.grid)
+    A = M.laplacian_5pt(a.grid, upwind=upwind)
     b = M.rhs_ones(A)
     for P in a.parts:
         d = DD(P, device=0, rank=a.rank, comm="loopback")
         d.set_system(A, method)
         d.set_division(DIV[a.division])
 
-        def run(flags):
-            return d.solve(b, restart=a.restart, max_iter=a.iters, tol=1e-300, flags=flags)
+        def run(name, flags):
+            return solve(d, name, b, restart=a.restart, max_iter=a.iters, tol=1e-300, flags=flags)
 
-        ms = {name: [] for name, _ in METHODS}
+        ms = {name: [] for name, _ in methods}
         short = {}
-        for name, f in METHODS:                         # warm-up
-            g = run(f)
+        for name, f in methods:                         # warm-up
+            g = run(name, f)
             if g["inner"] != a.iters:
                 short[name] = (g["ret"], g["inner"])
         for _ in range(a.reps):
-            for name, f in METHODS:
+            for name, f in methods:
                 if name not in short:
-                    ms[name].append(run(f)["solve_ms"])
+                    ms[name].append(run(name, f)["solve_ms"])
         info = d.info()
-        for name, f in METHODS:
+        for name, f in methods:
             if name in short:
-                emit(kind="time", grid=a.grid, parts=P, rank=a.rank, method=name, ended_early=short[name],
-                     us_per_iteration=None)
+                emit(kind="time", grid=a.grid, upwind=upwind, parts=P, rank=a.rank, method=name,
+                     ended_early=short[name], us_per_iteration=None)
                 continue
             med = statistics.median(ms[name])
-            emit(kind="time", grid=a.grid, parts=P, rank=a.rank, method=name, iterations=a.iters, reps=a.reps,
+            emit(kind="time", grid=a.grid, upwind=upwind, parts=P, rank=a.rank, method=name, iterations=a.iters,
+                 reps=a.reps,
                  division=a.division, solve_ms_median=round(med, 4), solve_ms_min=round(min(ms[name]), 4),
                  solve_ms_max=round(max(ms[name]), 4), us_per_iteration=round(med * 1e3 / a.iters, 3),
                  local_len=info["local_len"], halo_doubles=info["halo_doubles"])
-        for name, f in METHODS:                         # the families, in runs of their own
+        for name, f in methods:                         # the families, in runs of their own
             if name in short:
                 continue
             d.profile(True)
-            g = run(f)
+            g = run(name, f)
             fam = {}
             for k, fname in enumerate(PROF_NAMES):
                 cnt, tot = d.profile_get(k)
                 if cnt:
                     fam[fname] = {"marks": cnt, "us_per_iteration": round(tot * 1e3 / g["inner"], 3)}
             d.profile(False)
-            emit(kind="families", grid=a.grid, parts=P, rank=a.rank, method=name, iterations=g["inner"],
+            emit(kind="families", grid=a.grid, upwind=upwind, parts=P, rank=a.rank, method=name, iterations=g["inner"],
                  families=fam)
         d.close()
 
-    if a.count_grid:
+    if a.count_grid and a.bicgstab:
+        P = max(a.parts)
+        Ac = M.laplacian_5pt(a.count_grid, upwind=upwind)
+        bc = M.rhs_ones(Ac)
+        d = DD(P, device=0)
+        d.set_system(Ac, method)
+        d.set_division(DIV[a.division])
+        pair = (("bicgstab", ggmres.SOLVE_BICGSTAB), ("cgs2", ggmres.SOLVE_CGS2))
+        kw = dict(restart=a.restart, max_iter=20000, tol=a.tol)
+        last = {name: solve(d, name, bc, flags=f, **kw) for name, f in pair}      # warm-up
+        ms = {name: [] for name, _ in pair}
+        for _ in range(a.reps):
+            for name, f in pair:
+                last[name] = solve(d, name, bc, flags=f, **kw)
+                ms[name].append(last[name]["solve_ms"])
+        for name, _ in pair:
+            g = last[name]
+            emit(kind="count", grid=a.count_grid, upwind=upwind, parts=P, comm="local", method=name, ret=g["ret"],
+                 iterations=g["inner"], relres=g["relres"], reps=a.reps,
+                 solve_ms_all_shards_one_gpu=round(statistics.median(ms[name]), 3),
+                 solve_ms_min=round(min(ms[name]), 3), solve_ms_max=round(max(ms[name]), 3))
+        d.close()
+        s = ggmres.Solver(0)
+        s.set_matrix(Ac)
+        s.set_precond_ilu0()
+        s.set_division(DIV[a.division])
+        g = s.solve(bc, restart=a.restart, max_iter=20000, tol=a.tol, flags=ggmres.SOLVE_BICGSTAB)
+        emit(kind="count", grid=a.count_grid, upwind=upwind, parts=1, comm="single solver, natural order",
+             method="bicgstab", ret=g["ret"], iterations=g["inner"], relres=g["relres"],
+             solve_ms=round(g["solve_ms"], 3))
+        s.close()
+    elif a.count_grid:
         P = max(a.parts)
         Ac = M.laplacian_5pt(a.count_grid)
         bc = M.rhs_ones(Ac)

@@ -23,6 +23,10 @@ clock around the whole call(s) -- every one ends in a device synchronise -- and 
 median is reported as seconds per run and microseconds per iteration.  Before
 any time is printed the runs of a method must agree bit for bit in x, the ports
 and the iteration total.
+
+--bicgstab: the same three runs for BiCGStab steps alone, on the grid made
+nonsymmetric (M.laplacian_5pt(grid, upwind=--upwind)): the host loop around
+DD.solve_bicgstab against DD.transient_bicgstab_src without and with the hint.
 """
 import argparse
 import json
@@ -55,10 +59,12 @@ def main():
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--restart", type=int, default=32)
     p.add_argument("--tol", type=float, default=1e-7)
+    p.add_argument("--bicgstab", action="store_true")
+    p.add_argument("--upwind", type=float, default=0.2)
     a = p.parse_args()
 
     c, h = 1e-3, 1e-2
-    A = M.transient(M.laplacian_5pt(a.grid), c=c, h=h)
+    A = M.transient(M.laplacian_5pt(a.grid, upwind=a.upwind if a.bicgstab else 0.0), c=c, h=h)
     n = A.shape[0]
     cdiag = np.full(n, c / h)
     nodes, pulses = M.pulse_sources(n, h=h)
@@ -78,7 +84,7 @@ def main():
         for it in range(1, a.steps + 1):
             w = 0.0 + cdiag * x                     # xnr = 0; xnr += (C/h) x
             w[nodes] = uval[it] + w[nodes]          # one source per row: bu + xnr
-            r = d.solve(w, x0=x, flags=flags, **kw)
+            r = (d.solve_bicgstab if a.bicgstab else d.solve)(w, x0=x, flags=flags, **kw)
             x = r["x"]
             total += r["iters"]
             ret = r["ret"] or ret
@@ -91,13 +97,17 @@ def main():
         else:
             os.environ["GG_DD_TRANSIENT_HINT"] = "0"
         try:
-            return d.transient_src(a.steps, h, cdiag, nodes, sources, ports, np.zeros(n), flags=flags, **kw)
+            fn = d.transient_bicgstab_src if a.bicgstab else d.transient_src
+            return fn(a.steps, h, cdiag, nodes, sources, ports, np.zeros(n), flags=flags, **kw)
         finally:
             os.environ.pop("GG_DD_TRANSIENT_HINT", None)
 
-    for mname, flags in (("cg", ggmres.SOLVE_CG), ("cgs2", ggmres.SOLVE_CGS2)):
+    methods = (("cg", ggmres.SOLVE_CG), ("cgs2", ggmres.SOLVE_CGS2))
+    if a.bicgstab:
+        methods = (("bicgstab", ggmres.SOLVE_BICGSTAB),)
+    for mname, flags in methods:
         runs = [("host", lambda f=flags: host_loop(f)), ("loop", lambda f=flags: loop(f, False))]
-        if mname == "cg":
+        if mname != "cgs2":
             runs.append(("loop+hint", lambda f=flags: loop(f, True)))
         first = {name: fn() for name, fn in runs}                       # warm-up, and the bits
         ref = first["host"]
